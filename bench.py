@@ -27,6 +27,9 @@ EVERY rank checks sampled rooms of ITS OWN batch -- the output of the last timed
 ("parity_sample": rank 0's rooms in `per_room`, every rank's rooms / device / worst error in `ranks`, the worst over all
 ranks in `worst_rel_all_ranks`); a failure on any rank exits non-zero after the line is printed.  The oracle runs in worker
 processes while the GPU goes on with the next workload.
+`--dump-outputs DIR` writes what the headline's last timed step computed (rank 0's enhanced signals and masks, float32 .npy, a fixed
+seeded sample of rooms within DUMP_BYTES); every input is generated from fixed seeds, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import hashlib
@@ -42,6 +45,7 @@ sys.path.insert(0, REPO)
 # scheme, C5, to 3e-4: its float32 sums over 157 frames left room 199 at 2.3e-4.  Round 4 shortened the sums -- time sub-chunks across
 # the lanes of the room pass, float64 step-1 statistics -- and the relaxed bar is gone.)
 PARITY_TOL = 1.0e-4
+DUMP_BYTES = 60 << 20      # --dump-outputs: every array together, float32 (the .npy headers stay well inside the 64 MB cap)
 HBM_ACHIEVABLE = 6.3e12    # /opt/skills/guides/MI355X_MICROARCH.md: what a streaming kernel reaches; a stage "moving" more than that has a wrong byte model
 HBM_PEAK = 8.0e12          # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s measured achievable)
 BF16_MATRIX_PEAK = 2.5e15   # same guide: dense bf16 MFMA peak (the headline figures with 2:1 sparsity are never used)
@@ -377,8 +381,12 @@ def gather_rank_rows(rank, world, device_index, first_room, rooms_global, worst,
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps of the headline workload (at least 1)')
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the headline\'s last timed step computed (rank 0) as DIR/<name>.npy, float32: '
+                         'enhanced (rooms, nodes, length) and the masks it ran on; a fixed seeded sample of the rooms when the whole '
+                         f'batch exceeds {DUMP_BYTES >> 20} MiB')
     ap.add_argument('--config', default='C3', choices=sorted(CONFIGS), help='BASELINE.json configuration (shape defaults)')
     ap.add_argument('--rooms', type=int, default=None, help='rooms per GPU')
     ap.add_argument('--nodes', type=int, default=None)
@@ -423,6 +431,8 @@ def parse_args(argv=None):
                     help='no GPU work: every rank joins a gloo group, rank 0 prints n_gpus and the all-rank parity merge of fake per-rank '
                          'errors (covers the self-launch path and the all-rank bookkeeping on CPU)')
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps: at least one timed step')
     cfg = CONFIGS[args.config]
     plain = all(getattr(args, k) is None for k in ('rooms', 'nodes', 'mics', 'n_fft', 'iters', 'mask', 'online_every'))
     for k in ('rooms', 'nodes', 'mics', 'n_fft', 'iters', 'mask', 'online_every'):
@@ -610,6 +620,15 @@ def run_workload(name, w, steps, warmup, env, headline, n_parity_rank0, args):
         step()
     barrier()
     dt_local = time.perf_counter() - t0
+    if headline and args.dump_outputs and rank == 0:
+        # before anything below runs the path again: these are the buffers of the last timed step
+        got = {'enhanced': out}
+        if mask_kind == 'crnn':
+            got.update(mask_z=dnn['mz'], mask_w=dnn['mw'])
+        else:
+            got['mask'] = mask
+        rooms = dump_outputs(args.dump_outputs, got)
+        print(f'--dump-outputs: {sorted(got)} of {len(rooms)} of {R} rooms -> {args.dump_outputs}', file=sys.stderr)
     if headline:
         value, dt = dd.whole_job_throughput(units_per_step * steps, dt_local, world, device=env['cdev'])
     else:
@@ -1052,6 +1071,28 @@ def write_detail(full, path=None):
     return done
 
 
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: `arrays` (name -> tensor, the room as leading axis) as out_dir/<name>.npy in float32, at most `budget` bytes in all.
+    Every array keeps the same rooms: all of them when they fit, else a fixed seeded sample (ascending).  When one room alone is over the
+    budget, each array is cut further to a fixed seeded sample of its elements (ascending flat indices), in proportion to its size.
+    -> the rooms written."""
+    import numpy as np
+    import torch
+    R = next(iter(arrays.values())).shape[0]
+    per_room = sum(4 * a[0].numel() for a in arrays.values())
+    n = min(R, budget // per_room)
+    rng = np.random.default_rng(seed)
+    rooms = np.arange(R) if n == R else np.sort(rng.choice(R, max(n, 1), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        x = a.index_select(0, torch.as_tensor(rooms, device=a.device))
+        if n == 0:
+            keep = budget * a[0].numel() // per_room
+            x = x.reshape(-1)[torch.as_tensor(np.sort(rng.choice(x.numel(), keep, replace=False)), device=a.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), x.float().cpu().numpy())
+    return rooms.tolist()
+
+
 def exchange_object(R, K, Kl, T, F, iters, gather_ms, world, overlap, timed):
     """The line's `exchange` object (--shard nodes): one all-gather of z per step-2 iteration; every rank receives the other ranks' z
     (R (K - Kl) T F complex64) and sends its own R Kl T F block to each peer over that peer's link (xGMI is point-to-point)."""
@@ -1110,10 +1151,11 @@ def main(argv=None):
     rank, world, local_rank = dd.env_rank_world()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # started plainly: become the launcher of N ranks of this very command line (one process per GPU)
-        if not (args.selftest_launch or args.dry_collective):
+        # (with --single-device the launcher leaves the GPU alone: counting devices would open it in one more process than the ranks)
+        if not (args.selftest_launch or args.dry_collective or args.single_device):
             import torch
             have = torch.cuda.device_count()
-            if have < args.gpus and not args.single_device:
+            if have < args.gpus:
                 raise SystemExit(f'--gpus {args.gpus} but only {have} GPU(s) are visible')
         raise SystemExit(dd.launch_ranks(os.path.abspath(__file__), sys.argv[1:] if argv is None else list(argv), args.gpus))
     if args.gpus != world:

@@ -685,6 +685,7 @@ def check_c5_full_length(make_engine, rooms=(0, 6, 64, 100, 141, 199), K=8, M=8,
     launch geometry is pinned to the one the 200-room batch takes (one frame chunk in the step-1 statistics; the room pass has none), so
     that every room goes through exactly the arithmetic it goes through in the bench.  The oracles run in worker processes while the
     GPU computes.  (The iterated scheme is an extension: the reference is strictly two-step, tango.py:1-7; the oracle defines it.)"""
+    import multiprocessing as mp
     from concurrent.futures import ProcessPoolExecutor
     from disco_amd import synth
     data = [synth.make_room_numpy(r, K=K, M=M, L=L)[:3] for r in rooms]
@@ -692,7 +693,8 @@ def check_c5_full_length(make_engine, rooms=(0, 6, 64, 100, 141, 199), K=8, M=8,
     s = np.stack([d[1] for d in data])
     n = np.stack([d[2] for d in data])
     R = len(rooms)
-    with ProcessPoolExecutor(max_workers=R) as pool:
+    # spawn, not fork: a forked worker would inherit this process's open GPU device files (its HIP runtime is up by now)
+    with ProcessPoolExecutor(max_workers=R, mp_context=mp.get_context('spawn')) as pool:
         futs = [pool.submit(_c5_oracle_room, y[i], s[i, :, 0], n[i, :, 0], n_fft, iters) for i in range(R)]
         eng = make_engine(rooms=R, nodes=K, mics=M, length=L, n_fft=n_fft)
         eng.set_tuning(0, 1, 0, 0)

@@ -103,3 +103,38 @@ def test_flagged_bins_come_from_the_masks_alone():
     assert list(fb) == [1, 3]
     src = open(os.path.join(REPO, 'bench.py')).read()
     assert 'ILL_POSED' not in src and 'reported, not asserted' not in src
+
+
+def test_dump_outputs_fixed_sample_within_budget(tmp_path):
+    """--dump-outputs (bench.dump_outputs): float32 .npy files under the byte budget, the same rooms of every array, a seeded sample that
+    is the same from run to run; all rooms when they fit, a seeded sample of elements when one room alone is over the budget."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    arrays = {'enhanced': torch.randn(50, 2, 1000, generator=g), 'mask': torch.rand(50, 2, 9, 17, generator=g, dtype=torch.float64)}
+    per_room = 4 * (2 * 1000 + 2 * 9 * 17)
+
+    def dump(d, budget):
+        rooms = bench.dump_outputs(str(d), arrays, budget=budget)
+        got = {nm: np.load(d / f'{nm}.npy') for nm in arrays}
+        assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= budget
+        return rooms, got
+
+    rooms, got = dump(tmp_path / 'a', 10 * per_room + 5)
+    assert len(rooms) == 10 and rooms == sorted(set(rooms)) and all(0 <= r < 50 for r in rooms)
+    for nm, a in arrays.items():
+        assert np.array_equal(got[nm], a[rooms].float().numpy())
+    rooms2, got2 = dump(tmp_path / 'b', 10 * per_room + 5)
+    assert rooms2 == rooms and all(np.array_equal(got[nm], got2[nm]) for nm in arrays)
+    rooms, got = dump(tmp_path / 'c', 50 * per_room)
+    assert rooms == list(range(50)) and np.array_equal(got['enhanced'], arrays['enhanced'].numpy())
+    rooms, got = dump(tmp_path / 'd', per_room // 3)
+    assert len(rooms) == 1 and got['enhanced'].ndim == 1 and got['enhanced'].size > 0
+    assert np.isin(got['enhanced'], arrays['enhanced'][rooms[0]].numpy()).all()
+    _, again = dump(tmp_path / 'e', per_room // 3)
+    assert all(np.array_equal(got[nm], again[nm]) for nm in arrays)
+    assert bench.parse_args(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])

@@ -338,13 +338,17 @@ def test_reference_steps_state(make_engine):
 
 def test_engine_on_another_device():
     """Every entry point switches to the context's own device -- the plain memory helpers included (round-2 advice): an engine on
-    device 1 while device 0 is current must allocate, copy and compute on device 1 and leave device 0 current.  Needs two GPUs."""
+    device 1 while device 0 is current must allocate, copy and compute on device 1 and leave device 0 current.  On a box with ONE GPU
+    there is no device 1: the engine must be refused with the device named -- never run on device 0 instead -- and device 0 stays current."""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip('needs two GPUs')
     from disco_amd import _lib
-    from disco_amd.engine import Engine
+    from disco_amd.engine import DiscoError, Engine
     torch.cuda.set_device(0)
+    if torch.cuda.device_count() < 2:
+        with pytest.raises(DiscoError, match='no HIP device 1'):
+            Engine(rooms=2, nodes=1, mics=3, length=4000, device=1, lib=_lib.load())
+        assert torch.cuda.current_device() == 0
+        return
     rng = np.random.default_rng(0)
     x = rng.standard_normal((2, 3, 4000)).astype(np.float32)
     ref = Engine(rooms=2, nodes=1, mics=3, length=4000, device=0, lib=_lib.load()).stft(x).numpy()

@@ -291,7 +291,7 @@ def test_bench_self_launches_ranks():
     assert p.returncode != 0 and 'WORLD_SIZE' in (p.stderr + p.stdout)
 
 
-@pytest.mark.parametrize('world,nodes,iters', [(2, 4, 2), (4, 8, 1)])
+@pytest.mark.parametrize('world,nodes,iters', [(2, 4, 2), (4, 8, 1), (8, 8, 1)])
 def test_bench_dry_collective_exchange_fields(world, nodes, iters):
     """`python bench.py --gpus W --shard nodes --dry-collective` (round-5 VERDICT item 9): W self-launched gloo ranks run the z exchange of the
     node-sharded step on CPU tensors of the real per-rank size -- `iters` all-gathers per step into the rank-major buffer, every block
