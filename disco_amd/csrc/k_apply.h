@@ -296,10 +296,11 @@ static __global__ void k_maxpool_last4(const float* __restrict__ x, const float*
         const int q = (int)(i - r * nq);
         const float* p = x + r * row_len + 4 * q;
         const float b = bias ? bias[(r / rows_per_ch) % C] : 0.f;
-        // torch.nn.MaxPool2d propagates NaN, fmaxf drops it: the sum is NaN iff one of the four is
+        // torch.nn.MaxPool2d propagates NaN, fmaxf drops it: each candidate is tested on its own (their sum is also NaN for +inf
+        // with -inf, or for finite values that overflow both ways)
         const float mx = fmaxf(fmaxf(p[0], p[1]), fmaxf(p[2], p[3]));
-        const float any = (p[0] + p[1]) + (p[2] + p[3]);
-        out[i] = (any != any ? any : mx) + b;
+        const bool nan = (p[0] != p[0]) | (p[1] != p[1]) | (p[2] != p[2]) | (p[3] != p[3]);
+        out[i] = (nan ? __builtin_nanf("") : mx) + b;
     }
 }
 

@@ -67,10 +67,10 @@ static __global__ __launch_bounds__(256) void k_conv3x3_pool4_direct(const float
                 }
 #pragma unroll
             for (int o = 0; o < OCW; ++o) {
-                // torch.nn.MaxPool2d propagates NaN, fmaxf drops it: the sum is NaN iff one of the four is (k_maxpool_last4)
+                // torch.nn.MaxPool2d propagates NaN, fmaxf drops it: each candidate is tested on its own (k_maxpool_last4)
                 const float mx = fmaxf(fmaxf(acc[o][0], acc[o][1]), fmaxf(acc[o][2], acc[o][3]));
-                const float any = (acc[o][0] + acc[o][1]) + (acc[o][2] + acc[o][3]);
-                out[(((long long)b * O + o0 + o) * Tout + t0 + tt) * FQ + q] = (any != any ? any : mx) + bo[o];
+                const bool nan = (acc[o][0] != acc[o][0]) | (acc[o][1] != acc[o][1]) | (acc[o][2] != acc[o][2]) | (acc[o][3] != acc[o][3]);
+                out[(((long long)b * O + o0 + o) * Tout + t0 + tt) * FQ + q] = (nan ? __builtin_nanf("") : mx) + bo[o];
             }
         }
     }
@@ -100,7 +100,9 @@ static __global__ void k_crnn_features(const c32* __restrict__ X, const c32* __r
                 const int k = (int)(g % K), j = (c - 1) < k ? (c - 1) : c;            // the (c - 1)-th node other than k
                 a = Z[(((g / K) * K + j) * T + t) * (long long)F + f];
             }
-            v = fminf(fmaxf(sqrtf(a.x * a.x + a.y * a.y), lo), hi);
+            // |a|^2 with its fma written out: hipcc's contraction chose fma(a.x, a.x, a.y a.y) here, but its choice follows the code around it
+            const float m = sqrtf(fmaf(a.x, a.x, a.y * a.y));
+            v = m != m ? m : fminf(fmaxf(m, lo), hi);     // NaN passes, as np.clip / torch.clamp leave it (fmaxf would make it lo)
         }
         out[i] = v;
     }

@@ -1707,6 +1707,26 @@ def check_conv3x3_pool4(lib, device, shapes=((3, 1, 32, 30, 257), (2, 4, 32, 19,
     nan = torch.isnan(out.cpu())
     want_nan = torch.isnan(torch.nn.functional.max_pool2d(torch.nn.functional.conv2d(x, w, b, padding=(0, 1)), (1, 4)))
     assert torch.equal(nan, want_nan) and int(nan.sum()) == 32 * 3 * 2
+    # windows of candidates that are not plain numbers (centre tap only, 2 x +-3e38 inputs): +inf and -inf in one window -> +inf;
+    # finite candidates whose sum overflows both ways -> the largest (the zero taps see only finite inputs: no 0 x inf)
+    x = torch.zeros((1, 1, 5, 257))
+    big_ = 3e38
+    x[0, 0, 1, 0:4] = torch.tensor([big_, -big_, 0.0, 0.0])                 # x 2: +inf, -inf
+    x[0, 0, 2, 8:12] = torch.tensor([big_, big_, -big_, -big_]) * 0.5        # x 2: +-3e38, finite
+    x[0, 0, 2, 12:16] = torch.tensor([-big_, -big_, big_, big_]) * 0.5
+    w = torch.zeros((32, 1, 3, 3))
+    w[:, 0, 1, 1] = 2.0
+    b = torch.linspace(-1, 1, 32)
+    out = torch.empty((1, 32, 3, 64), dtype=torch.float32, device=device)
+    xd, wd, bd = x.to(device), w.to(device), b.to(device)
+    assert lib.disco_conv3x3_pool4(None, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), 1, 1, 32, 5, 257, out.data_ptr(), None) == 0
+    if xd.is_cuda:
+        torch.cuda.synchronize()
+    got = out.cpu()
+    want = torch.nn.functional.max_pool2d(torch.nn.functional.conv2d(x.double(), w.double(), b.double(), padding=(0, 1)), (1, 4)).float()
+    assert not bool(torch.isnan(want).any()) and not bool(torch.isnan(got).any()), torch.nonzero(torch.isnan(got))[:8]
+    assert torch.equal(got, want), torch.nonzero(got != want)[:8]
+    assert bool((got[0, :, 0, 0] == float('inf')).all()) and bool((got[0, :, 1, 2:4] == want[0, :, 1, 2:4]).all()) and bool(torch.isfinite(got[0, :, 1, 2:4]).all())
     # refused, not mis-computed
     assert lib.disco_conv3x3_pool4(None, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), 1, 32, 64, 5, 64, out.data_ptr(), None) == -2      # 32 input channels
     assert lib.disco_conv3x3_pool4(None, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), 1, 1, 32, 5, 513, out.data_ptr(), None) == -2      # 513 bins
@@ -1749,6 +1769,274 @@ def check_crnn_features(lib, device, R=2, K=3, M=2, T=9, F=17):
         assert e < 3e-7 and float(got[:, :, :, :pad[0]].abs().max()) == 0.0 and float(got[:, :, :, pad[0] + T:].abs().max()) == 0.0, e
         assert float(got[0, 0, 0, pad[0], 0]) == float(torch.tensor(STFT_MIN, dtype=torch.float32)) if mic < M else True
         errs.append(e)
+    # NaN passes the clip, as np.clip / torch.clamp leave it (a NaN spectrum must not turn into silence); +-inf clips to hi.  X's NaN sits
+    # on microphone 0 only, z's reaches the other nodes' channels
+    Xn, zn = X.clone(), z.clone()
+    Xn[1, 2, 4, 5, 0] = complex(float('nan'), 0.5)
+    Xn[0, 1, 6, 9, :] = complex(float('inf'), 1.0)
+    Xn[1, 0, 7, 2, :] = complex(-1.0, float('-inf'))
+    zn[1, 0, 3, 7] = complex(float('nan'), -2.0)
+    zn[0, 2, 2, 2] = complex(float('-inf'), 0.0)
+    for mic in (0, 1):
+        pad = (10, 10)
+        Tp = pad[0] + T + pad[1]
+        Xd, zd = Xn.to(device), zn.to(device)
+        out = torch.empty((R * K, K, Tp, F), dtype=torch.float32, device=device)
+        assert lib.disco_crnn_features(None, Xd.data_ptr(), zd.data_ptr(), R, K, M, T, F, mic, pad[0], pad[1], STFT_MIN, STFT_MAX, out.data_ptr(),
+                                       _stream(Xd)) == 0
+        _sync(Xd)
+        got = out.cpu().view(R, K, K, Tp, F)[:, :, :, pad[0]:pad[0] + T]
+        want = torch.empty((R, K, K, T, F))
+        want[:, :, 0] = Xn[..., mic].abs()
+        for k in range(K):
+            want[:, k, 1:] = get_z_for_mask(zn.abs().transpose(0, 1), None, k, K, 'zs_hat').transpose(0, 1)
+        want = want.clamp(STFT_MIN, STFT_MAX)
+        nan = torch.isnan(want)
+        assert int(nan.sum()) == (K - 1) + (mic == 0), int(nan.sum())
+        assert torch.equal(torch.isnan(got), nan), torch.nonzero(torch.isnan(got) != nan).tolist()
+        assert float(got[0, 1, 0, 6, 9]) == float(got[1, 0, 0, 7, 2]) == float(torch.tensor(STFT_MAX)) == float(got[0, 0, 2, 2, 2])
+        e = float(((got - want).abs() / want.abs().clamp_min(1e-30))[~nan].max())
+        assert e < 3e-7, e
+        errs.append(e)
     assert lib.disco_crnn_features(None, None, None, R, K, M, T, F, 0, 1, 1, 0.0, 1.0, out.data_ptr(), None) == -1
     assert lib.disco_crnn_features(None, Xd.data_ptr(), None, R, K, M, T, F, M, 1, 1, 0.0, 1.0, out.data_ptr(), None) == -1       # microphone out of range
     return errs
+
+
+def _sync(t):
+    import torch
+    if t.is_cuda:
+        torch.cuda.synchronize()
+
+
+def _stream(t):
+    import torch
+    return torch.cuda.current_stream().cuda_stream if t.is_cuda else None
+
+
+def _assert_same_floats(got, want, what):
+    """Bit-level agreement of two float tensors of one shape: NaN at the same places, every other value equal (inf included)."""
+    import torch
+    got, want = got.cpu(), want.cpu()
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    gn, wn = torch.isnan(got), torch.isnan(want)
+    assert torch.equal(gn, wn), (what, 'NaN at', torch.nonzero(gn != wn)[:8].tolist())
+    bad = (got != want) & ~wn
+    assert not bool(bad.any()), (what, 'differs at', torch.nonzero(bad)[:8].tolist(), got[bad][:8].tolist(), want[bad][:8].tolist())
+
+
+def _gru_gates_ref(gi, gh, h, H):
+    """One GRU step's gate arithmetic in float64 (torch.nn.GRU's definition): gi (n, 3H), gh (n, 3H) or (3H,), h (n, H) or None."""
+    gi, gh = gi.double(), gh.double()
+    gh = gh.expand(gi.shape[0], -1)
+    r = 1.0 / (1.0 + (-(gi[:, :H] + gh[:, :H])).exp())
+    z = 1.0 / (1.0 + (-(gi[:, H:2 * H] + gh[:, H:2 * H])).exp())
+    n = (gi[:, 2 * H:] + r * gh[:, 2 * H:]).tanh()
+    return (1 - z) * n + (0 if h is None else z * h.double())
+
+
+def check_gru_gates(lib, device, cases=((301, 1), (37, 19), (5, 256)), chain=(64, 24, 32), big=False, tol=1e-6, chain_tol=5e-6):
+    """disco_gru_gates (the pointwise half of predict_masks' GRU step) against the float64 gate arithmetic, for every (n, H) of `cases`:
+    the first step (gh NULL with gh_bias, h_prev NULL), gh without h_prev, the full step with gi a time slice of an [n][steps][3H] tensor
+    and with gi rows padded with NaN beyond 3H (never read), h_out aliasing h_prev (bit-identical to the separate buffer), saturating
+    pre-activations (+-1e30, +-inf in gi) with a finite answer, and a NaN that must reach exactly its own output.  Then the chained
+    form of predict_masks -- one input GEMM, a recurrent GEMM + disco_gru_gates per step -- against torch.nn.GRU in float64 over 8
+    and 15 steps (chain = (n, input size, H)): pins the gate order and where the biases go.  big: n = 70 000, H = 256, more elements
+    than one launch covers, with pre-activations N(0, 4): float32 evaluation of the tanh argument gi_n + r gh_n errs by about
+    2^-23 (|gi_n| + |gh_n|) where the two cancel, and 17.9 M draws of N(0, 16) find such a pair (1.05e-6 under the emulator).
+    Returns the largest errors seen."""
+    import torch
+    errs = {}
+
+    def call(gi, gh, bias, h, out, n, H):
+        rc = lib.disco_gru_gates(None, gi.data_ptr(), gi.stride(0), None if gh is None else gh.data_ptr(), None if bias is None else bias.data_ptr(),
+                                 None if h is None else h.data_ptr(), out.data_ptr(), n, H, _stream(out))
+        assert rc == 0, (rc, n, H)
+        _sync(out)
+        return out
+
+    def err(name, got, want):
+        e = float((got.double().cpu() - want.cpu()).abs().max())
+        errs[name] = max(errs.get(name, 0.0), e)
+        assert e < tol, (name, e)
+
+    for n, H in cases:
+        g = torch.Generator().manual_seed(n * 1000 + H)
+        S, st = 8, 5
+        gi_all = (torch.randn((n, S, 3 * H), generator=g) * 4).to(device)              # pre-activations ~ N(0, 16)
+        gi = gi_all[:, st]                                                                # rows at stride S * 3H
+        gh = (torch.randn((n, 3 * H), generator=g) * 4).to(device)
+        bias = torch.randn((3 * H,), generator=g).to(device)
+        h = (torch.rand((n, H), generator=g) * 2 - 1).to(device)
+        out = torch.empty((n, H), device=device)
+        err('first_step', call(gi, None, bias, None, out, n, H), _gru_gates_ref(gi, bias, None, H))
+        err('no_h_prev', call(gi, gh, None, None, out, n, H), _gru_gates_ref(gi, gh, None, H))
+        err('full_step', call(gi, gh, None, h, out, n, H), _gru_gates_ref(gi, gh, h, H))
+        want = out.clone()
+        padded = torch.full((n, 3 * H + 5), float('nan'), device=device)                 # NaN beyond 3H: a stray read shows
+        padded[:, :3 * H] = gi
+        _assert_same_floats(call(padded, gh, None, h, out, n, H), want, ('padded gi', n, H))
+        h2 = h.clone()
+        _assert_same_floats(call(gi, gh, None, h2, h2, n, H), want, ('h_out aliasing h_prev', n, H))
+        # saturating and infinite pre-activations (the float64 answer is finite), then one NaN per gate in gi
+        gi_s, gh_s = gi.clone(), gh.clone()
+        k = min(n * H, 6)
+        rows, cols = torch.arange(k, device=device) % n, torch.arange(k, device=device) % H
+        for part, vals in ((0, (1e30, -1e30, float('inf'), float('-inf'), 1e30, float('-inf'))),
+                           (1, (float('-inf'), 1e30, -1e30, float('inf'), float('inf'), -1e30)),
+                           (2, (1e30, float('inf'), float('-inf'), -1e30, float('-inf'), 1e30))):
+            gi_s[rows, part * H + cols] = torch.tensor(vals[:k], device=device)
+        gh_s[rows[::2], 2 * H + cols[::2]] = -1e30
+        want_s = _gru_gates_ref(gi_s, gh_s, h, H)
+        assert bool(torch.isfinite(want_s).all())
+        err('saturating', call(gi_s, gh_s, None, h, out, n, H), want_s)
+        err('saturating_first_step', call(gi_s, None, bias, None, out, n, H), _gru_gates_ref(gi_s, bias, None, H))
+        gi_n = gi.clone()
+        nan_at = [(0, 0), ((n - 1), H + (H - 1)), (n // 2, 2 * H + H // 2)]
+        for r_, c_ in nan_at:
+            gi_n[r_, c_] = float('nan')
+        got = call(gi_n, gh, None, h, out, n, H).cpu()
+        want_nan = torch.zeros((n, H), dtype=torch.bool)
+        for r_, c_ in nan_at:
+            want_nan[r_, c_ % H] = True
+        assert torch.equal(torch.isnan(got), want_nan), ('NaN', n, H, torch.nonzero(torch.isnan(got)).tolist())
+        err('nan_elsewhere', got[~want_nan], _gru_gates_ref(gi, gh, h, H).cpu()[~want_nan])
+
+    # the recurrence as predict_masks runs it, against torch.nn.GRU (float64, same weights)
+    n, I, H = chain
+    for S in (8, 15):
+        torch.manual_seed(S)
+        gru = torch.nn.GRU(I, H, batch_first=True).double()
+        x = torch.randn((n, S, I), dtype=torch.float64)
+        with torch.no_grad():
+            want = gru(x)[0][:, -1]
+        w_ih, w_hh, b_ih, b_hh = (p.detach().float().to(device) for p in (gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0))
+        gi = torch.addmm(b_ih, x.float().to(device).reshape(-1, I), w_ih.t()).view(n, S, 3 * H)
+        h = None
+        for st in range(S):
+            gh = None if h is None else torch.addmm(b_hh, h, w_hh.t())
+            h = call(gi[:, st], gh, b_hh if gh is None else None, h, torch.empty((n, H), device=device), n, H)
+        e = float((h.double().cpu() - want).abs().max())
+        errs[f'chain_{S}'] = e
+        assert e < chain_tol, (S, e)
+
+    if big:
+        n, H = 70000, 256
+        g = torch.Generator(device=device).manual_seed(5)
+        gi = torch.randn((n, 3 * H), device=device, generator=g) * 2
+        gh = torch.randn((n, 3 * H), device=device, generator=g) * 2
+        h = torch.rand((n, H), device=device, generator=g) * 2 - 1
+        out = torch.empty((n, H), device=device)
+        e = float((call(gi, gh, None, h, out, n, H).double() - _gru_gates_ref(gi, gh, h, H)).abs().max())
+        errs['big'] = e
+        assert e < tol, ('big', e)
+        del gi, gh, h, out
+
+    # refused, not mis-computed
+    gi, out, bias = torch.zeros((4, 12), device=device), torch.empty((4, 4), device=device), torch.zeros(12, device=device)
+    assert lib.disco_gru_gates(None, gi.data_ptr(), 11, None, bias.data_ptr(), None, out.data_ptr(), 4, 4, None) == -1        # gi_stride < 3H
+    assert lib.disco_gru_gates(None, gi.data_ptr(), 12, None, bias.data_ptr(), None, out.data_ptr(), 0, 4, None) == -1        # n < 1
+    assert lib.disco_gru_gates(None, gi.data_ptr(), 12, None, bias.data_ptr(), None, out.data_ptr(), 4, 0, None) == -1        # H < 1
+    assert lib.disco_gru_gates(None, None, 12, None, bias.data_ptr(), None, out.data_ptr(), 4, 4, None) == -1                  # no gi
+    assert lib.disco_gru_gates(None, gi.data_ptr(), 12, None, None, None, out.data_ptr(), 4, 4, None) == -1                    # no gh, no gh_bias
+    return errs
+
+
+def check_maxpool_last4(lib, device, big=False):
+    """disco_maxpool_last4 (MaxPool2d((1, 4)) floor mode + per-channel bias) against torch's max_pool2d then + bias in float32: the same
+    operations, so equal bit for bit, NaN where torch has NaN.  Row lengths 4, 7, 64, 257 with huge values in the dropped tail, no bias,
+    a (B, C, rows) layout whose channel index wraps, and windows whose candidates are non-finite or overflow when summed.  big: more than
+    2^28 outputs (the grid-stride loop makes a second pass, as at C4's second block; a 4.3 GB input)."""
+    import torch
+
+    def run(x, bias):
+        B, C, R, L = x.shape
+        out = torch.empty((B, C, R, L // 4), device=x.device)
+        rc = lib.disco_maxpool_last4(None, x.data_ptr(), None if bias is None else bias.data_ptr(), B * C * R, L, R, C, out.data_ptr(), _stream(x))
+        assert rc == 0, (rc, x.shape)
+        _sync(x)
+        return out
+
+    def ref(x, bias):
+        y = torch.nn.functional.max_pool2d(x, (1, 4))
+        return y if bias is None else y + bias.view(1, -1, 1, 1)
+
+    g = torch.Generator().manual_seed(4)
+    for shape in ((2, 3, 5, 4), (2, 3, 5, 7), (1, 4, 9, 64), (2, 2, 3, 257), (3, 5, 6, 16)):
+        x = torch.randn(shape, generator=g)
+        tail = shape[-1] % 4
+        if tail:
+            x[..., -tail:] = 3e38                              # floor mode drops these: a leak shows as 3e38
+        bias = torch.randn((shape[1],), generator=g) * 10      # a different bias per channel
+        xd, bd = x.to(device), bias.to(device)
+        _assert_same_floats(run(xd, bd), ref(x, bias), ('bias', shape))
+        _assert_same_floats(run(xd, None), ref(x, None), ('no bias', shape))
+    # windows that are not plain numbers: torch propagates NaN and takes +inf over -inf; a sum of the candidates says NaN for both
+    inf, big_ = float('inf'), 3e38
+    wins = [[inf, -inf, 0, 0], [big_, big_, -big_, -big_], [-big_, -big_, big_, big_], [float('nan'), 1, 2, 3], [-inf] * 4,
+            [1, 2, 3, float('nan')], [-inf, inf, -big_, big_], [0.5, -2, 7, 1]]
+    x = torch.tensor(wins, dtype=torch.float32).view(1, 2, 1, 16)
+    bias = torch.tensor([0.25, -1.5])
+    for b_ in (bias, None):
+        got = run(x.to(device), None if b_ is None else b_.to(device))
+        _assert_same_floats(got, ref(x, b_), ('non-finite', b_ is not None))
+    assert run(x.to(device), None).cpu().view(-1)[:3].tolist() == [inf, float(torch.tensor(big_)), float(torch.tensor(big_))]
+    if big:
+        B, C, R, L = 409, 64, 642, 64                           # 16.8 M rows of 16 pooled bins: 2^28 + 444 416 outputs
+        gd = torch.Generator(device=device).manual_seed(6)
+        x = torch.randn((B, C, R, L), device=device, generator=gd)
+        x.view(-1)[[0, 5, x.numel() // 2 + 3, x.numel() - 1]] = float('nan')
+        x.view(-1)[-8:-4] = torch.tensor([inf, -inf, 0, 0], device=device)
+        bias = torch.randn((C,), device=device, generator=gd)
+        got = run(x, bias)
+        want = ref(x, bias)
+        assert got.numel() > 1 << 28
+        nan_g, nan_w = torch.isnan(got), torch.isnan(want)
+        assert torch.equal(nan_g, nan_w) and int(nan_g.sum()) == 4
+        assert bool(((got == want) | nan_w).all())
+        del x, got, want, nan_g, nan_w
+        torch.cuda.empty_cache()
+    # refused, not mis-computed
+    x, out, bias = torch.zeros(64, device=device), torch.empty(16, device=device), torch.zeros(2, device=device)
+    assert lib.disco_maxpool_last4(None, x.data_ptr(), None, 16, 3, 1, 1, out.data_ptr(), None) == -1                 # row_len < 4
+    assert lib.disco_maxpool_last4(None, x.data_ptr(), bias.data_ptr(), 16, 4, 8, 0, out.data_ptr(), None) == -1     # bias, no channels
+    return True
+
+
+def check_crnn_windows(lib, device):
+    """disco_crnn_windows against predict_masks' own strided fallback (crnn.py: `as_strided` over (nb, T, c_used, W Fy)), bit for bit:
+    n_keep 4, 2048 ('mid': 8 GRU steps x 256) and 3840 (= C W 4, 'last'), a feature map with more frames than T + W - 1, and several
+    signals of one channel and one window.  Misaligned or inconsistent arguments are refused."""
+    import torch
+    W, Fy = 15, 4
+
+    def run(feat, T, n_keep):
+        nb, C, Tp, _ = feat.shape
+        out = torch.empty((nb * T, n_keep), device=feat.device)
+        rc = lib.disco_crnn_windows(None, feat.data_ptr(), nb, C, Tp, T, W, n_keep, out.data_ptr(), _stream(feat))
+        assert rc == 0, (rc, feat.shape, T, n_keep)
+        _sync(feat)
+        return out
+
+    def ref(feat, T, n_keep):
+        nb, C, Tp, _ = feat.shape
+        c_used = min(C, -(-n_keep // (W * Fy)))
+        win = feat.as_strided((nb, T, c_used, W * Fy), (feat.stride(0), Fy, feat.stride(1), 1)).reshape(nb * T, c_used * W * Fy)
+        return win[:, :n_keep]
+
+    g = torch.Generator().manual_seed(7)
+    for (nb, C, T, extra, n_keep) in ((2, 64, 9, 0, 4), (2, 64, 9, 0, 2048), (2, 64, 9, 0, 3840), (3, 64, 5, 6, 2048), (3, 64, 4, 3, 3840),
+                                      (3, 1, 1, 0, 60), (4, 1, 1, 2, 4)):
+        feat = torch.randn((nb, C, T + W - 1 + extra, Fy), generator=g)
+        _assert_same_floats(run(feat.to(device), T, n_keep), ref(feat, T, n_keep), (nb, C, T, extra, n_keep))
+    # refused, not mis-computed
+    feat, out = torch.zeros((1, 3, 20, 4), device=device), torch.empty((64, 128), device=device)     # room for a call that is not refused
+    f, o = feat.data_ptr(), out.data_ptr()
+    assert lib.disco_crnn_windows(None, f, 1, 2, 20, 6, W, 120, o, None) == 0
+    _sync(out)
+    assert lib.disco_crnn_windows(None, f, 1, 2, 20, 6, W, 6, o, None) == -1            # n_keep % 4
+    assert lib.disco_crnn_windows(None, f, 1, 2, 20, 6, W, 124, o, None) == -1          # n_keep > C W 4
+    assert lib.disco_crnn_windows(None, f, 1, 2, 20, 7, W, 120, o, None) == -1          # Tp < T + W - 1
+    assert lib.disco_crnn_windows(None, f + 4, 1, 2, 19, 5, W, 120, o, None) == -1      # feat off 16-byte alignment
+    assert lib.disco_crnn_windows(None, f, 1, 2, 20, 6, W, 120, o + 4, None) == -1      # out off 16-byte alignment
+    return True

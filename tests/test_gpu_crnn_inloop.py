@@ -115,6 +115,57 @@ def test_conv3x3_pool4_vs_torch():
     print(pc.check_conv3x3_pool4(_lib.load(), 'cuda:0'))
 
 
+def test_gru_gates_vs_float64():
+    """The GRU step's gate arithmetic (disco_gru_gates) against float64, chained over 8 and 15 steps against torch.nn.GRU, and at
+    n = 70 000 x H = 256 (more elements than one launch pass covers)."""
+    import torch
+    torch.cuda.set_device(0)
+    print(pc.check_gru_gates(_lib.load(), 'cuda:0', chain=(4096, 256, 256), big=True))
+
+
+def test_maxpool_last4_vs_torch():
+    """MaxPool (1, 4) + bias (disco_maxpool_last4) against torch bit for bit, non-finite windows, and more than 2^28 outputs."""
+    import torch
+    torch.cuda.set_device(0)
+    assert pc.check_maxpool_last4(_lib.load(), 'cuda:0', big=True)
+
+
+def test_crnn_windows_vs_strided():
+    """The recurrent layer's input windows (disco_crnn_windows) against predict_masks' strided fallback, bit for bit."""
+    import torch
+    torch.cuda.set_device(0)
+    assert pc.check_crnn_windows(_lib.load(), 'cuda:0')
+
+
+@pytest.mark.parametrize('fused', [True, False])
+@pytest.mark.parametrize('tag,n_ch', [('sc', 1), ('mc', 4)])
+@pytest.mark.parametrize('ftp', ['mid', 'last'])
+def test_predict_masks_float32_vs_float64_production_shape(golden_dir, tag, n_ch, ftp, fused):
+    """predict_masks in float32 -- every HIP helper of the network on its path -- against the same trained network in float64 on the
+    same GPU (all helpers are gated on float32: that run is plain torch), at a shape past every single-pass launch: 300 signals (chunks
+    of 256 + 44) of 300 frames, so 76 800 GRU rows per step."""
+    import copy
+    import os
+    import torch
+    from disco_amd.dnn.crnn import build_crnn
+    gold = np.load(os.path.join(golden_dir, 'crnn_ref.npz'))
+    sd = {k[len(tag) + 4:]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith(f'{tag}_sd_')}
+    dev = torch.device('cuda', 0)
+    model = build_crnn(n_ch=n_ch, state_dict=sd).to(dev).eval()
+    model.fused_first_block = fused
+    ref_model = copy.deepcopy(model).double()
+    B, T, F = 300, 300, 257
+    g = torch.Generator(device=dev).manual_seed(n_ch * 10 + fused)
+    level = torch.exp(2.0 * torch.randn((B, n_ch, T, 1), device=dev, generator=g))               # loud and near-silent frames
+    mag = torch.randn((B, n_ch, T, F), device=dev, generator=g).abs() * level
+    mask = model.predict_masks(mag, frame_to_pred=ftp)
+    want = ref_model.predict_masks(mag.double(), frame_to_pred=ftp)
+    assert mask.dtype == torch.float32 and mask.shape == (B, T, F)
+    err = float((mask.double() - want).abs().max())
+    print(tag, ftp, 'fused' if fused else 'library', 'max |mask32 - mask64|', err)
+    assert err < 2e-5, err
+
+
 @pytest.mark.parametrize('fused', [True, False])
 @pytest.mark.parametrize('tag,n_ch', [('sc', 1), ('mc', 4)])
 @pytest.mark.parametrize('ftp,nt', [('mid', None), ('last', None), ('mid', 'scale_to_unit_norm'), ('mid', 'scale_to_1'), ('last', 'center_and_scale')])

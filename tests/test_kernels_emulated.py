@@ -109,6 +109,18 @@ def test_emu_conv3x3_pool4():
     print(pc.check_conv3x3_pool4(emu_build.load_emu(), 'cpu'))
 
 
+def test_emu_gru_gates():
+    print(pc.check_gru_gates(emu_build.load_emu(), 'cpu'))
+
+
+def test_emu_maxpool_last4():
+    print(pc.check_maxpool_last4(emu_build.load_emu(), 'cpu'))
+
+
+def test_emu_crnn_windows():
+    print(pc.check_crnn_windows(emu_build.load_emu(), 'cpu'))
+
+
 def test_emu_ism_pinned(make_engine):
     print(pc.check_ism_pinned_hip(make_engine))
 
