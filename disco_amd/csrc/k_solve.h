@@ -12,8 +12,11 @@
 // LDS form -- P = 5 ... 8, the online kernel, k_mwf_variants, and option "solve_dpp" = 0.)
 // Mapping: a group of G = 4 / 8 / 16 lanes owns one problem, lane j owns column j.  Everything is float64:
 // cooperative Cholesky through LDS, two forward substitutions (column j of L^-1 Rxx, then column j of C),
-// then the DOMINANT eigenpair only (rank = 1 needs nothing else) by repeated squaring of C / tr C, which converges
+// then the TOP eigenpair only (rank = 1 needs nothing else) by repeated squaring of C / tr C, which converges
 // to v0 v0^H; d0 is the Rayleigh quotient q^H Rxx q of the back-substituted q = L^-H v0.
+// Squaring finds the eigenvalue of largest MAGNITUDE.  That is the top one for a positive semi-definite C (every pencil the
+// library forms itself: masked covariances).  An indefinite C (callers passing Ryy - Rnn) is caught after the fact -- see
+// group_dominant -- and solved again on the shifted matrix C + ||C||_F I, whose spectrum is >= 0 and in the same order as C's.
 #pragma once
 #include "common.h"
 #include "k_cov.h"
@@ -40,6 +43,13 @@ namespace disco {
 #endif
 #ifndef DISCO_SQUARINGS_MAX
 #define DISCO_SQUARINGS_MAX 40
+#endif
+// The exit test above is sound once B is a normalised square (positive semi-definite, unit trace: tau <= 1), i.e. from the
+// second check on, and at the first check only when C itself is PSD.  A PSD C that stops at the first check keeps a square with
+// tr(B^2) >= 0.968 (tau_0 > 0.8 puts the top eigenvalue of B_0 above 0.887); an indefinite C can stop there with tau_0 > 1, or
+// with tau_0 in (0.8, 1] and its top pair unresolved.  Below this value the kept square of a first-check exit is not trusted.
+#ifndef DISCO_KEPT_TAU_MIN
+#define DISCO_KEPT_TAU_MIN 0.95
 #endif
 // A group of G <= 16 lanes never spans waves, so its LDS hand-offs need no s_barrier: a wave's DS instructions execute
 // in issue order; what has to be prevented is the compiler moving a read above the write it depends on through another
@@ -149,6 +159,19 @@ __device__ __forceinline__ void solve_load_row(const SolveSrc& src, long long pi
     }
 }
 
+// A copy of a pencil's row that the compiler cannot prove equal to the original.  The second pass over a flagged pencil (see
+// group_dominant) starts from such copies: computed from the same values it would be merged with the first pass, whose
+// intermediates (the whitened matrix, the factor) would then stay live through its squarings.
+template <int P>
+__device__ __forceinline__ void opaque_row(const c32* in, c32* out) {
+#pragma unroll
+    for (int c = 0; c < P; ++c) {
+        out[c] = in[c];
+        DISCO_CONSUME(out[c].x);
+        DISCO_CONSUME(out[c].y);
+    }
+}
+
 // ---- building blocks of the group solves (a group of G lanes, lane j owns row / column j; Lm, Ym: the group's LDS) ----------
 
 // Cholesky factor of the Hermitian matrix whose row j lane j passes in `row` (only the lower triangle is used), left in Lm:
@@ -217,10 +240,29 @@ __device__ __forceinline__ int group_cholesky_factor(c64* Lm, const int j) {
 
 // Dominant eigenvector of the Hermitian matrix whose column j lane j passes in g (destroyed): v0 (unit norm, every lane gets
 // all of it).  Returns false when the matrix is zero or not finite (v0 = e0 then).
-template <int P>
-__device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::YW], const int j, c64* v0) {
+// Dominant = of largest |eigenvalue|.  `suspect` (group-uniform) is set where that may not be the TOP eigenpair or may not have
+// converged, which needs an indefinite matrix: a finite non-zero matrix with tr <= 0, or a stop at the first check whose kept
+// square has tr(B^2) < DISCO_KEPT_TAU_MIN.  The caller adds the third case, a negative Rayleigh quotient.  SHIFT (the second pass
+// of a wave with a flagged pencil): where `shift`, the same on M + ||M||_F I (positive semi-definite, same eigenvectors, same order
+// of the eigenvalues); elsewhere exactly the first pass again.
+template <int P, bool SHIFT = false>
+__device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::YW], const int j, c64* v0, bool* suspect = nullptr,
+                                               const bool shift = false) {
     constexpr int G = SolveGeom<P>::G;
     bool done;
+    double fro = 0.0;                                          // ||M||_F^2
+#pragma unroll
+    for (int i = 0; i < P; ++i) fro = fma(g[i].x, g[i].x, fma(g[i].y, g[i].y, fro));
+#pragma unroll
+    for (int off = G / 2; off >= 1; off >>= 1) fro += __shfl_xor(fro, off, G);
+    DISCO_CONSUME(fro);                                        // formed HERE: sunk to its use, it kept the unscaled matrix live
+    if constexpr (SHIFT) {
+        const double sh = sqrt(fro);                           // >= |every eigenvalue|
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+            if (i == j) g[i].x = shift ? g[i].x + sh : g[i].x;
+    }
+    bool tr_bad, exit0 = false;
     {
         double trl = 0.0;
 #pragma unroll
@@ -233,6 +275,7 @@ __device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::Y
 #pragma unroll
         for (int i = 0; i < P; ++i) g[i] = ok ? zscale(g[i], rt) : make_double2(0.0, 0.0);
         done = !ok;
+        tr_bad = !(trl > 0.0) && fro > 0.0 && fro < 1.7e308;
     }
     for (int it = 0; it < DISCO_SQUARINGS_MAX; ++it) {
         DISCO_GROUP_SYNC();                                    // previous readers of Ym (Y above / the last square) are done
@@ -277,8 +320,9 @@ __device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::Y
 #pragma unroll
             for (int i = 0; i < P; ++i) g[i] = zmul(nn[i], itau);
         }
+        if (it == 0) exit0 = !done && (1.0 - tc.x < DISCO_SQUARING_DONE);
         done = done || (1.0 - tc.x < DISCO_SQUARING_DONE) || !(den > 0.0);
-        if (!__any(!done)) break;                              // wave-uniform exit                              // wave-uniform exit: finished groups keep squaring a projector
+        if (!__any(!done)) break;                              // wave-uniform exit: finished groups keep squaring a projector
     }
 
     // L is read again by the back substitution below: make the compiler re-load it from LDS there instead of carrying
@@ -299,6 +343,13 @@ __device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::Y
             best = ob;
             bj = oj;
         }
+    }
+    if (suspect) {
+        double kept = nrm;                                     // tr(B^2) of the kept square
+#pragma unroll
+        for (int off = G / 2; off >= 1; off >>= 1) kept += __shfl_xor(kept, off, G);
+        DISCO_CONSUME(kept);
+        *suspect = P > 1 && (tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN));
     }
     const bool have = best > 0.0;                          // false: C = 0 or not finite -> v0 = e0 (d0 is clamped below)
     const double rb = have ? rsqrt64(best) : 0.0;
@@ -375,14 +426,13 @@ __device__ __forceinline__ void group_forward_substitute(c64* b, const c64* Lm) 
 // (rowB); Lm / Ym are the group's two LDS matrices.  Returns this lane's component of t1 and the scalar gain
 // d0 / (d0 + mu)  (w_j = t1_j * gain).  Contains wave-level fences and wave-wide votes: every lane of a wave must call it,
 // the same number of times.  REENTER: a fence first, so that a previous call's readers of Lm / Ym are done (callers in a loop).
-template <int P, bool REENTER>
-__device__ __forceinline__ void gevd_solve_group(const c32* rowA, const c32* rowB, c64* Lm, c64 (*Ym)[SolveGeom<P>::YW],
-                                                 const int j, const double mu, c64& t1_j, double& gain_out) {
+// Everything after the Cholesky factor: whitening, top eigenpair, back substitution, t1 and the gain.  Returns `suspect` (see
+// group_dominant): the pencil must be solved again, shifted (SHIFT and `shift`), which keeps Lm and re-forms C from rowA.
+template <int P, bool SHIFT>
+__device__ __forceinline__ bool gevd_pass_group(const c32* rowA, const c64* Lm, c64 (*Ym)[SolveGeom<P>::YW], const int j, const double mu,
+                                                c64& t1_j, double& gain_out, const bool shift = false) {
     constexpr int G = SolveGeom<P>::G;
     using SG = SolveGeom<P>;
-    if constexpr (REENTER) DISCO_GROUP_SYNC();
-    group_cholesky<P>(rowB, Lm, j);
-
     // ---- column j of Y = L^-1 Rxx   (Rxx[i][j] = conj(Rxx[j][i]): read row j, contiguous)
     c64 y[P];
 #pragma unroll
@@ -423,14 +473,16 @@ __device__ __forceinline__ void gevd_solve_group(const c32* rowA, const c32* row
     // the full diagonalisation a Jacobi solver performs (what this kernel did before: 5-7 sweeps of P(P-1)/2 rotations)
     // is not needed: with B_0 = C / tr C,  B_{k+1} = B_k^2 / tr(B_k^2)  converges to v0 v0^H and the sub-dominant
     // directions decay like (d1/d0)^(2^k) -- 3-6 squarings for the ratios 0.5-0.9 met on real covariances, P^2 complex
-    // multiply-adds per lane each (a Jacobi SWEEP costs ~5 P^2).  tau_k = tr(B_k^2) = ||B_k||_F^2 <= 1 doubles as the
-    // normaliser and the convergence measure: 1 - tau ~ 2 (d1/d0)^(2^k); once it is below DISCO_SQUARING_DONE a few power
+    // multiply-adds per lane each (a Jacobi SWEEP costs ~5 P^2).  tau_k = tr(B_k^2) = ||B_k||_F^2 doubles as the normaliser and
+    // the convergence measure -- <= 1 for a PSD B_k, which every B_k with k >= 1 is, and B_0 when C is PSD (an indefinite C is
+    // flagged by group_dominant and solved again, shifted) --: 1 - tau ~ 2 (d1/d0)^(2^k); once it is below DISCO_SQUARING_DONE a few power
     // steps on the square just formed finish the job at 1/P of the price of a squaring each.  Lane j owns column j; the columns meet through the group's LDS matrix Ym (wave-level
     // fences only: a group never spans waves).  An exactly repeated top eigenvalue never converges (tau -> 1/m) and
     // stops at the iteration cap with a vector of the dominant subspace, which is all any solver can return there.
     // The loop is wave-uniform (vote on the exit): groups that are done keep their B and idle.
     c64 v0[P];
-    const bool have = group_dominant<P>(g, Ym, j, v0);
+    bool suspect = false;
+    const bool have = group_dominant<P, SHIFT>(g, Ym, j, v0, SHIFT ? nullptr : &suspect, shift);
 
     c64 q[P];
     group_back_substitute<P>(v0, Lm, q);
@@ -459,6 +511,21 @@ __device__ __forceinline__ void gevd_solve_group(const c32* rowA, const c32* row
         if (i == j) t1_j = zmul(q[i], gsc);
     }
     gain_out = gain;
+    return suspect || d0 < 0.0;                               // the dominant eigenvalue is negative: not the top one
+}
+
+template <int P, bool REENTER>
+__device__ __forceinline__ void gevd_solve_group(const c32* rowA, const c32* rowB, c64* Lm, c64 (*Ym)[SolveGeom<P>::YW],
+                                                 const int j, const double mu, c64& t1_j, double& gain_out) {
+    if constexpr (REENTER) DISCO_GROUP_SYNC();
+    group_cholesky<P>(rowB, Lm, j);
+    const bool suspect = gevd_pass_group<P, false>(rowA, Lm, Ym, j, mu, t1_j, gain_out);
+    // a flagged pencil re-solves its whole wave (wave-uniform vote; never taken by a PSD pencil): the others repeat the first pass, so
+    // that nothing of it has to stay live through the second
+    if (__any(suspect)) {
+        DISCO_GROUP_SYNC();                                   // the first pass's readers of Ym are done
+        (void)gevd_pass_group<P, true>(rowA, Lm, Ym, j, mu, t1_j, gain_out, suspect);
+    }
 }
 
 // (A mixed-precision form of this solve -- float32 squarings on packed instructions and a float64 Rayleigh-quotient finish, option
@@ -500,7 +567,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(SolveGeom<P>::THREADS, SolveGeom
 // ---- the other two branches of intern_filter (internal_formulas.py:45-54, 74-76): dead on the hot path, offered so that the
 // function's whole surface (its DEFAULT type is 'r1-mwf') is there.  Same mapping and the same group primitives:
 //   'mwf'    : Wint = ((Rnn + Rxx)^-1 Rxx)[:, 0]                               -- one Cholesky solve
-//   'r1-mwf' : Rxx1 = |Dmax| x x^H (dominant eigenpair of Rxx alone); P = Rnn^-1 Rxx1; Wint = P[:, 0] / (mu + tr P)
+//   'r1-mwf' : Rxx1 = |Dmax| x x^H (top eigenpair of Rxx alone, Dmax its eigenvalue); P = Rnn^-1 Rxx1; Wint = P[:, 0] / (mu + tr P)
 //              = |Dmax| conj(x_0) u / (mu + |Dmax| x^H u),  u = Rnn^-1 x      -- squaring + one Cholesky solve
 // (np.linalg.lstsq's minimum-norm answer for a singular matrix is NOT reproduced: the pivot floor of group_cholesky applies.)
 constexpr int FILTER_R1_MWF = 1, FILTER_MWF = 2;
@@ -531,21 +598,36 @@ __global__ __launch_bounds__(SolveGeom<P>::THREADS, SolveGeom<P>::WPE) void k_mw
         for (int i = 0; i < P; ++i)
             rhs[i] = make_double2((double)__shfl(rowA[i].x, 0, G), -(double)__shfl(rowA[i].y, 0, G));
     } else {                                    // dominant eigenpair of Rxx: column j = conj(row j)
+        // the reference takes D.max() of the real eigenvalues: the TOP eigenpair, which squaring finds directly only where the
+        // dominant one is positive; the others are solved again on the shifted Rxx (group_dominant)
+        auto rayleigh = [&](const c64* x) {                   // Dmax = x^H Rxx x: lane j forms (Rxx x)_j from its row
+            c64 sj = make_double2(0.0, 0.0), xj = make_double2(0.0, 0.0);
+#pragma unroll
+            for (int c = 0; c < P; ++c) {
+                sj.x = fma((double)rowA[c].x, x[c].x, fma(-(double)rowA[c].y, x[c].y, sj.x));
+                sj.y = fma((double)rowA[c].x, x[c].y, fma((double)rowA[c].y, x[c].x, sj.y));
+                if (c == j) xj = x[c];
+            }
+            double e = j < P ? xj.x * sj.x + xj.y * sj.y : 0.0;
+#pragma unroll
+            for (int off = G / 2; off >= 1; off >>= 1) e += __shfl_xor(e, off, G);
+            return e;
+        };
         c64 g[P];
 #pragma unroll
         for (int i = 0; i < P; ++i) g[i] = make_double2((double)rowA[i].x, -(double)rowA[i].y);
-        group_dominant<P>(g, s_Y[slot], j, rhs);
-        // Dmax = x^H Rxx x: lane j forms (Rxx x)_j from its row
-        c64 sj = make_double2(0.0, 0.0), xj = make_double2(0.0, 0.0);
+        bool suspect = false;
+        group_dominant<P>(g, s_Y[slot], j, rhs, &suspect);
+        double e = rayleigh(rhs);
+        suspect = suspect || e < 0.0;
+        if (__any(suspect)) {                                 // wave-uniform: the wave again, flagged pencils shifted
+            c32 ra[P];
+            opaque_row<P>(rowA, ra);
 #pragma unroll
-        for (int c = 0; c < P; ++c) {
-            sj.x = fma((double)rowA[c].x, rhs[c].x, fma(-(double)rowA[c].y, rhs[c].y, sj.x));
-            sj.y = fma((double)rowA[c].x, rhs[c].y, fma((double)rowA[c].y, rhs[c].x, sj.y));
-            if (c == j) xj = rhs[c];
+            for (int i = 0; i < P; ++i) g[i] = make_double2((double)ra[i].x, -(double)ra[i].y);
+            group_dominant<P, true>(g, s_Y[slot], j, rhs, nullptr, suspect);
+            e = rayleigh(rhs);
         }
-        double e = j < P ? xj.x * sj.x + xj.y * sj.y : 0.0;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) e += __shfl_xor(e, off, G);
         scale = fabs(e);
     }
     group_cholesky<P>(rowB, Lm, j);

@@ -139,18 +139,15 @@ __device__ __forceinline__ void group_stage_rows(const float4* stage, int j, c64
     DISCO_GROUP_SYNC();                                 // the block is reused (transposition of Y) once every lane has its rows
 }
 
-template <int P, bool FROM_PART>
-__global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) void k_gevd_mwf_r1_dpp(SolveSrc src, long long n_prob, double mu,
-                                                                                              c32* __restrict__ w_out, c32* __restrict__ t1_out) {
+// One solve of the pencil of this lane's row, from loading it to this lane's t1 and the gain.  Returns `suspect` (group_dominant,
+// k_solve.h: C may be indefinite and the dominant eigenpair not the top one); SHIFT: the second pass of a wave with such a pencil,
+// which solves it again from its loading on, on C + ||C||_F I where `shift`, and repeats the first pass elsewhere.
+template <int P, bool FROM_PART, bool SHIFT>
+__device__ __forceinline__ bool gevd_pass_dpp(const SolveSrc& src, const long long pid, const int j, const bool live, c64* Mm, const double mu,
+                                              c64& t1_out, double& gain_out, const bool shift = false) {
     using DG = DppSolveGeom<P>;
     constexpr int PW = DG::PW;
-    __shared__ c64 s_M[DG::PROBS][DG::BLOCK];
-    const int j = threadIdx.x & 15;                     // row / column owned by this lane
-    const int slot = threadIdx.x >> 4;
-    const long long pid = (long long)blockIdx.x * DG::PROBS + slot;
-    const bool live = pid < n_prob;
     const bool col = live && j < P;
-    c64* Mm = s_M[slot];
 
     c32 rowA[P];                                        // row j of Rxx in float32: all that crosses the squarings (the Rayleigh quotient's)
     c64 a[P];                                           // row j of Rnn, then of its Cholesky factor
@@ -254,9 +251,20 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) voi
     DISCO_DPP_SETTLE();
 
     // ---- dominant eigenpair of C by repeated squaring of B = C / tr C (see gevd_solve_group / group_dominant for the reasoning:
-    // complex trace as the normaliser, DISCO_SQUARING_DONE, the power-step finish, the wave-uniform exit)
-    bool done;
+    // complex trace as the normaliser, DISCO_SQUARING_DONE, the power-step finish, the wave-uniform exit, what is flagged `suspect`)
+    bool done, tr_bad, exit0 = false;
     {
+        double fj = 0.0;                                       // ||C||_F^2
+#pragma unroll
+        for (int i = 0; i < P; ++i) fj = fma(g[i].x, g[i].x, fma(g[i].y, g[i].y, fj));
+        double fro = BcReal(fj).sum();
+        DISCO_CONSUME(fro);                            // formed HERE: sunk to its use, it kept the unscaled matrix live
+        if constexpr (SHIFT) {
+            const double sh = sqrt(fro);
+#pragma unroll
+            for (int i = 0; i < P; ++i)
+                if (i == j) g[i].x = shift ? g[i].x + sh : g[i].x;
+        }
         double dj = 0.0;
 #pragma unroll
         for (int i = 0; i < P; ++i)
@@ -267,6 +275,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) voi
 #pragma unroll
         for (int i = 0; i < P; ++i) g[i] = zsel(ok, zscale(g[i], rt), make_double2(0.0, 0.0));
         done = !ok;
+        tr_bad = !(trl > 0.0) && fro > 0.0 && fro < 1.7e308;
     }
     for (int it = 0; it < DISCO_SQUARINGS_MAX; ++it) {
         DISCO_DPP_SETTLE();
@@ -292,6 +301,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) voi
 #pragma unroll
             for (int i = 0; i < P; ++i) g[i] = zmul(nn[i], itau);
         }
+        if (it == 0) exit0 = !done && (1.0 - tc.x < DISCO_SQUARING_DONE);
         done = done || (1.0 - tc.x < DISCO_SQUARING_DONE) || !(den > 0.0);
         if (!__any(!done)) break;
     }
@@ -299,12 +309,15 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) voi
 
     // ---- B ~ v0 v0^H: the longest column (lowest index among equals); lane j needs ITS component of it, B[j][bj] = conj(B[bj][j])
     c64 v;
-    bool have;
+    bool have, suspect;
     {
         double nrm = 0.0;
 #pragma unroll
         for (int i = 0; i < P; ++i) nrm += g[i].x * g[i].x + g[i].y * g[i].y;
         const BcReal nv(nrm);
+        double kept = nv.sum();                        // tr(B^2) of the kept square (summed by every lane: DPP under a uniform EXEC)
+        DISCO_CONSUME(kept);
+        suspect = tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN);
         double best = nv.template get<0>();
         int bj = 0;
         static_for<1, P>([&](auto K) {
@@ -374,8 +387,38 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) voi
     const c64 v00 = BcVec(v).template get<0>();
     const double dcl = fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA);
     const c64 gsc = make_double2(l00 * v00.x, -l00 * v00.y);   // L[0,0] conj(v0[0]) = (Q^-1)[0,0]
-    const double gain = dcl / (dcl + mu);
-    const c64 t1 = zmul(q, gsc);
+    gain_out = dcl / (dcl + mu);
+    t1_out = zmul(q, gsc);
+    return suspect || d0 < 0.0;                               // the dominant eigenvalue is negative: not the top one
+}
+
+template <int P, bool FROM_PART>
+__global__ DISCO_KERNEL_ALIGN __launch_bounds__(DppSolveGeom<P>::THREADS, 2) void k_gevd_mwf_r1_dpp(SolveSrc src, long long n_prob, double mu,
+                                                                                              c32* __restrict__ w_out, c32* __restrict__ t1_out) {
+    using DG = DppSolveGeom<P>;
+    __shared__ c64 s_M[DG::PROBS][DG::BLOCK];
+    const int j = threadIdx.x & 15;                     // row / column owned by this lane
+    const int slot = threadIdx.x >> 4;
+    const long long pid = (long long)blockIdx.x * DG::PROBS + slot;
+    const bool live = pid < n_prob;
+    const bool col = live && j < P;
+    c64* Mm = s_M[slot];
+    c64 t1;
+    double gain;
+    const bool suspect = gevd_pass_dpp<P, FROM_PART, false>(src, pid, j, live, Mm, mu, t1, gain);
+    // a flagged pencil re-solves its whole wave (wave-uniform vote; never taken by a PSD pencil): the others repeat the first pass, so
+    // that nothing of it has to stay live through the second
+    if (__any(suspect)) {
+        DISCO_GROUP_SYNC();                             // the first pass's readers of the block are done
+        // opaque lane / pencil indices: the second pass reloads and recomputes everything instead of being merged with the first
+        // (which would keep the first pass's loads and factor live through its squarings; see opaque_row, k_solve.h)
+        int j2 = j;
+        long long pid2 = pid;
+        DISCO_CONSUME(j2);
+        DISCO_CONSUME(pid2);
+        DISCO_DPP_SETTLE();
+        (void)gevd_pass_dpp<P, FROM_PART, true>(src, pid2, j2, pid2 < n_prob, Mm, mu, t1, gain, suspect);
+    }
     if (col) {
         if (t1_out) t1_out[pid * P + j] = make_float2((float)t1.x, (float)t1.y);
         w_out[pid * P + j] = make_float2((float)(t1.x * gain), (float)(t1.y * gain));

@@ -142,9 +142,12 @@ __device__ __forceinline__ void thread_cholesky(BD bd, BO bo, double* Ld, double
 // 2 x 98 + 112 + 49: two waves per SIMD instead of one; P = 8 runs without scratch).
 // Whitening C = L^-1 Rxx L^-H as LAPACK's zhegs2 does it (itype 1, lower): in place on the Hermitian half, P^3 / 2 complex multiply-adds
 // where the column-by-column form of round 2 took 1.2 P^3.
-// w, t1: this problem's P filter entries.  Contains a wave-wide vote: every lane of the wave must call it (dead lanes pass Rxx = 0, Rnn = I).
-template <int P, bool RECOMPUTE, bool SQ32, class LA, class LB>
-__device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, const double mu, c64* w, c64* t1) {
+// t1: this problem's P entries, gain: d0 / (d0 + mu).  Returns `suspect` (group_dominant, k_solve.h: C may be indefinite and the
+// dominant eigenpair not the top one); SHIFT: the second pass of a wave with such a pencil, which solves it again on C + ||C||_F I
+// where `shift` and repeats the first pass elsewhere.  Float64 squarings only.
+template <int P, bool RECOMPUTE, bool SQ32, bool SHIFT, class LA, class LB>
+__device__ __forceinline__ bool gevd_solve_thread_pass(LA load_a, LB load_b, const double mu, c64* t1, double& gain_out, const bool shift = false) {
+    static_assert(!(SQ32 && SHIFT), "the shifted pass squares in float64");
     constexpr int NO = P > 1 ? P * (P - 1) / 2 : 1;
     auto lo = [](int i, int k) { return i * (i - 1) / 2 + k; };
     auto f2z = [](c32 v) { return make_double2((double)v.x, (double)v.y); };
@@ -154,6 +157,7 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
     c64 Lo[NO];
     float a_d[P], b_d[P];
     c32 a_o[NO], b_o[NO];
+    if constexpr (SHIFT) asm volatile("" ::: "memory");   // the second pass loads again (not merged with the first: see gevd_solve_group)
     load_b(b_d, b_o);
     load_a(a_d, a_o);
     auto ad = [&](int i) { return (double)a_d[i]; };
@@ -205,6 +209,20 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
         }
     }
     // ---- dominant eigenpair by repeated squaring of B = C / tr C (see k_solve.h); tau = tr(B^2) = ||B||_F^2 is real here
+    double fro = 0.0;                                            // ||C||_F^2
+#pragma unroll
+    for (int i = 0; i < P; ++i) fro = fma(B.d[i], B.d[i], fro);
+#pragma unroll
+    for (int q = 0; q < NO; ++q) fro = fma(2.0 * B.o[q].x, B.o[q].x, fma(2.0 * B.o[q].y, B.o[q].y, fro));
+    DISCO_CONSUME(fro);          // formed HERE: sunk to its use at the end, it kept the unscaled B live through the squarings
+    if constexpr (SHIFT) {
+        const double sh = sqrt(fro);
+#pragma unroll
+        for (int i = 0; i < P; ++i) B.d[i] = shift ? B.d[i] + sh : B.d[i];
+        tr = shift ? tr + P * sh : tr;
+    }
+    const bool tr_bad = !(tr > 0.0) && fro > 0.0 && fro < 1.7e308;
+    bool exit0 = false;
     const bool ok = tr > 0.0 && tr < 1.7e308;
     {
         const double rt = ok ? rcp64(tr) : 0.0;
@@ -331,12 +349,14 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
 #pragma unroll
             for (int q = 0; q < NO; ++q) B.o[q] = zscale(S.o[q], rtau);
         }
+        if (it == 0) exit0 = !done && (1.0 - tau < DISCO_SQUARING_DONE);
         done = done || (1.0 - tau < DISCO_SQUARING_DONE) || !(tau > 0.0);
     }
     }
     // ---- B = v0 v0^H: the longest column (ties: lowest index), normalised
     c64 v0[P];
     bool have;
+    double kept = 0.0;                                           // tr(B^2) of the kept square (float64 form)
     if constexpr (SQ32 && P > 1) {
         have = have32;
 #pragma unroll
@@ -351,6 +371,7 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
                 const c64 b = B.at(i, j);
                 nj += b.x * b.x + b.y * b.y;
             }
+            kept += nj;
             if (nj > best) {
                 best = nj;
 #pragma unroll
@@ -358,6 +379,7 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
             }
         }
         have = best > 0.0;
+        DISCO_CONSUME(kept);     // (as fro above: formed here, not from a B kept live to the end)
         const double rb = have ? rsqrt64(best) : 0.0;
 #pragma unroll
         for (int i = 0; i < P; ++i) v0[i] = have ? zscale(v0[i], rb) : make_double2(i == 0 ? 1.0 : 0.0, 0.0);
@@ -403,7 +425,7 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
         DISCO_CONSUME(v0[0].x);
         load_b(b_d, b_o);
         load_a(a_d, a_o);
-        thread_cholesky<P>(bd, bo, Ld, rL, Lo);
+            thread_cholesky<P>(bd, bo, Ld, rL, Lo);
     }
     c64 q[P];
 #pragma unroll
@@ -427,13 +449,26 @@ __device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, cons
     }
     d0 = have ? d0 : 0.0;
     const double dcl = fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA);
-    const double gain = dcl / (dcl + mu);
+    gain_out = dcl / (dcl + mu);
     const c64 gsc = make_double2(Ld[0] * v0[0].x, -Ld[0] * v0[0].y);
 #pragma unroll
-    for (int i = 0; i < P; ++i) {
-        t1[i] = zmul(q[i], gsc);
-        w[i] = zscale(t1[i], gain);
+    for (int i = 0; i < P; ++i) t1[i] = zmul(q[i], gsc);
+    // (the SQ32 form is reached only from the online mode, whose pencils are PSD by construction: it flags nothing)
+    return !SQ32 && P > 1 && (tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN) || d0 < 0.0);
+}
+
+// w, t1: this problem's P filter entries.  Contains a wave-wide vote: every lane of the wave must call it (dead lanes pass Rxx = 0, Rnn = I).
+template <int P, bool RECOMPUTE, bool SQ32, class LA, class LB>
+__device__ __forceinline__ void gevd_solve_thread_acc(LA load_a, LB load_b, const double mu, c64* w, c64* t1) {
+    double gain;
+    const bool suspect = gevd_solve_thread_pass<P, RECOMPUTE, SQ32, false>(load_a, load_b, mu, t1, gain);
+    if constexpr (!SQ32 && P > 1) {
+        // a flagged pencil re-solves its whole wave (wave-uniform vote; never taken by a PSD pencil): the others repeat the first pass,
+        // so that nothing of it has to stay live through the second
+        if (__any(suspect)) (void)gevd_solve_thread_pass<P, RECOMPUTE, false, true>(load_a, load_b, mu, t1, gain, suspect);
     }
+#pragma unroll
+    for (int i = 0; i < P; ++i) w[i] = zscale(t1[i], gain);
 }
 
 // the same with both matrices handed over in registers as (diag, strict lower triangle) in float32 (the online kernel's state)

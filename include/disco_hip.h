@@ -213,15 +213,18 @@ int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float* mask,
                      disco_c32* Rss, disco_c32* Rnn, disco_stream s);
 
 /* intern_filter(Rxx, Rnn, mu, type='gevd', rank=1) -- internal_formulas.py:56-73, batched:
- * top generalized eigenpair of each Hermitian pencil (float64 Cholesky whitening + repeated squaring),
- * eigenvalue clamped to [eps, 1e6], w = q d/(d+mu) (Q^-1)[0,0], t1 = q (Q^-1)[0,0].
+ * top (algebraically largest) generalized eigenpair of each Hermitian pencil, Rnn positive definite, Rxx any Hermitian
+ * matrix (Ryy - Rnn included): float64 Cholesky whitening + repeated squaring, solved again on a shifted matrix where Rxx
+ * is indefinite.  Eigenvalue clamped to [eps, 1e6], w = q d/(d+mu) (Q^-1)[0,0], t1 = q (Q^-1)[0,0]; where every
+ * eigenvalue is <= 0, d = eps and w ~ 0.  An exactly repeated top eigenvalue yields some vector of its eigenspace.
  * Rss, Rnn: [n_prob][P][P]  ->  w, t1: [n_prob][P]  (t1 may be NULL).  1 <= P <= 16. */
 int disco_gevd_mwf_r1(disco_ctx* ctx, const disco_c32* Rss, const disco_c32* Rnn, int64_t n_prob, int P,
                       float mu, disco_c32* w, disco_c32* t1, disco_stream s);
 
 /* intern_filter's other two branches (internal_formulas.py:45-54 'r1-mwf' -- the function's DEFAULT type -- and :74-76 'mwf');
  * neither is reached by offline_tango, both are here so that the whole function is:
- *   DISCO_FILTER_R1_MWF  Rxx1 = |Dmax| x x^H (dominant eigenpair of Rxx); P = Rnn^-1 Rxx1; w = P[:, 0] / (mu + trace P)
+ *   DISCO_FILTER_R1_MWF  Rxx1 = |Dmax| x x^H (top eigenpair of Rxx: Dmax its largest eigenvalue, as D.max());
+ *                        P = Rnn^-1 Rxx1; w = P[:, 0] / (mu + trace P)
  *   DISCO_FILTER_MWF     w = ((Rnn + Rxx)^-1 Rxx)[:, 0]
  * Rxx, Rnn [n_prob][P][P] -> w [n_prob][P]; t1 of these branches is e_1 (internal_formulas.py:43), the caller's to fill. */
 #define DISCO_FILTER_R1_MWF 1

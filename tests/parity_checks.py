@@ -992,6 +992,132 @@ def check_solver_small_gap(make_engine, sizes=(2, 4, 7, 15)):
     return out
 
 
+def _indefinite_spectra(rng, P):
+    """Generalized spectra (descending) of the indefinite-pencil check, by case.  (a)-(c) are what the squaring alone gets wrong: the
+    dominant eigenvalue (largest |d|) is negative, the first tau = tr(B^2) test is fooled, or the trace is not positive."""
+    cases = {'d_psd': np.concatenate([[2.0], rng.uniform(0.0, 1.2, P - 1)])}
+    if P == 1:
+        cases['e_nonpositive'] = np.array([-0.7])
+        return {k: np.sort(v)[::-1] for k, v in cases.items()}
+    cases['a_dominant_negative'] = np.concatenate([[0.5], rng.uniform(-1.5, 0.3, P - 2), [-2.0]])
+    for r in (0.3, 0.6, 0.9):                           # top positive and dominant, the next largest |d| negative: |d1 / d0| = r
+        cases[f'b_negative_second_{r}'] = np.concatenate([[3.0], 3.0 * r * rng.uniform(-0.9, 0.9, P - 2), [-3.0 * r]])
+    m = P - 2
+    if m >= 3:
+        # {1, s (m times), -0.9} with tau_0 = (1.81 + m s^2) / (0.1 + m s)^2 = 0.9: the first test stops the squaring at once, with the
+        # top pair unresolved and tau_0 <= 1
+        a, b, c = 0.9 * m * m - m, 0.18 * m, 0.009 - 1.81
+        sv = (-b + np.sqrt(b * b - 4 * a * c)) / (2 * a)
+        cases['b_first_test_fooled'] = np.concatenate([[1.0], np.full(m, sv), [-0.9]])
+    cases['c_negative_trace'] = np.concatenate([[0.5], rng.uniform(-2.0, -0.6, P - 1)])
+    cases['e_nonpositive'] = rng.uniform(-2.0, -0.1, P)
+    return {k: np.sort(v)[::-1] for k, v in cases.items()}
+
+
+def check_solver_indefinite(make_engine, sizes=range(1, 17), option=None, value=None, per_case=9, cross=2, seed=29):
+    """Indefinite Hermitian pencils (Rxx = Ryy - Rnn, as a drop-in caller of intern_filter passes them): the solver must return the TOP
+    (algebraically largest) generalized eigenpair, clamped, as internal_formulas.py:56-73 does -- not the dominant one, which is what
+    repeated squaring finds.  Every case of _indefinite_spectra for each P, mixed in one launch whose size is not a multiple of the
+    pencils per block or wave; `option` = `value` picks the route (solve_thread 0/1 for P = 5..8, solve_dpp 0/1 for P = 9..16).
+    Reference: the float64 closed form on the same complex64 inputs, itself checked against mo.intern_filter on `cross` pencils per case.
+    Bar: 2e-6 / (1 - gap), gap = 1 - (d0 - d1) / max|d| -- d1 / d0 for a PSD spectrum, as in check_solver_small_gap.  All d <= 0 (case e):
+    every eigenvalue clamps to eps, so only |w| <= 1e-10 |t1| and finiteness are asserted, not the direction."""
+    rng = np.random.default_rng(seed)
+    eng = make_engine(rooms=1, nodes=1, mics=1, length=1024)
+    if option is not None:
+        eng.set_option(option, value)
+        assert eng.get_option(option) == value
+    out = {}
+    for P in sizes:
+        spectra = _indefinite_spectra(rng, P)
+        names, Rxx, Rnn = [], [], []
+        for name, d in spectra.items():
+            A, B = _pencil_with_spectrum(rng, per_case, P, d)
+            names += [name] * per_case
+            Rxx.append(A)
+            Rnn.append(B)
+        Rxx, Rnn, names = np.concatenate(Rxx), np.concatenate(Rnn), np.array(names)
+        if len(names) % 4 == 0:                         # ragged last block / wave for every route
+            Rxx, Rnn, names = Rxx[:-1], Rnn[:-1], names[:-1]
+        order = rng.permutation(len(names))
+        Rxx, Rnn, names = Rxx[order].astype(np.complex64), Rnn[order].astype(np.complex64), names[order]
+        w, t1 = eng.gevd_mwf_r1(Rxx, Rnn, mu=1.0)
+        w, t1 = w.numpy().astype(np.complex128), t1.numpy().astype(np.complex128)
+        assert np.all(np.isfinite(w)) and np.all(np.isfinite(t1)), P
+        wr, t1r, _ = mo.gevd_mwf_r1_hermitian(Rxx, Rnn, 1.0)
+        for name, d in spectra.items():
+            sel = names == name
+            if name.startswith('e_'):
+                ratio = np.linalg.norm(w[sel], axis=-1) / np.linalg.norm(t1[sel], axis=-1)
+                assert ratio.max() <= 1e-10, (P, name, ratio.max())
+                out[(P, name)] = float(ratio.max())
+                continue
+            for i in np.flatnonzero(sel)[:cross]:       # the closed form is the reference's own branch on a Hermitian pencil
+                wi, (t1i, _) = mo.intern_filter(Rxx[i].astype(np.complex128), Rnn[i].astype(np.complex128), mu=1, type='gevd', rank=1)
+                assert relerr(wi, wr[i]) < 1e-9 and relerr(t1i, t1r[i]) < 1e-9, (P, name, relerr(wi, wr[i]))
+            gap = 1.0 - (d[0] - d[1]) / np.abs(d).max() if P > 1 else 0.0
+            bar = 2e-6 / (1.0 - gap)
+            e = max((np.linalg.norm(w[sel] - wr[sel], axis=-1) / np.linalg.norm(wr[sel], axis=-1)).max(),
+                    (np.linalg.norm(t1[sel] - t1r[sel], axis=-1) / np.linalg.norm(t1r[sel], axis=-1)).max())
+            out[(P, name)] = float(e)
+            assert e < bar, (P, option, value, name, e, bar)
+    return out
+
+
+def _mwf_variant_ref(Rxx, Rnn, mu, type):
+    """mo.intern_filter's 'mwf' / 'r1-mwf' branches restated for (..., P, P) Hermitian float64 batches: np.linalg.lstsq of a regular
+    matrix is its solve; 'r1-mwf' keeps the eigenpair of D.max() over the real eigenvalues (the algebraically largest) and scales it by |Dmax|."""
+    Rxx, Rnn = Rxx.astype(np.complex128), Rnn.astype(np.complex128)
+    if type == 'mwf':
+        return np.linalg.solve(Rnn + Rxx, Rxx[..., :, :1])[..., 0]
+    D, X = np.linalg.eigh(Rxx)
+    x = X[..., :, -1]
+    R1 = np.abs(D[..., -1])[..., None, None] * x[..., :, None] * np.conjugate(x)[..., None, :]
+    Pm = np.linalg.solve(Rnn, R1)
+    return Pm[..., :, 0] / (mu + np.trace(Pm, axis1=-2, axis2=-1))[..., None]
+
+
+def check_mwf_variants(make_engine, sizes=range(1, 17), n=37, seed=31, tol=2e-6):
+    """disco_mwf_filter ('mwf' and 'r1-mwf', csrc/k_mwf_variants) on (2, n) batches -- every slot of a block carries a pencil, the last
+    block is ragged -- at mu 1 and 0.3, with PSD, indefinite (top positive, dominant negative) and negative-definite Rxx mixed in one
+    launch.  Rnn + Rxx stays positive definite (Rnn covers Rxx's negative part), as the 'mwf' branch's Cholesky needs.  Reference:
+    _mwf_variant_ref in float64 on the same complex64 inputs, checked against mo.intern_filter itself on a few pencils; bar: `tol`
+    relative per pencil."""
+    rng = np.random.default_rng(seed)
+    eng = make_engine(rooms=1, nodes=1, mics=1, length=1024)
+    out = {}
+    for P in sizes:
+        N = 2 * n
+        kind = rng.integers(0, 3, N)                    # 0: PSD, 1: indefinite, 2: negative definite
+        d = np.empty((N, P))
+        for i in range(N):
+            if kind[i] == 0:
+                d[i] = np.concatenate([[2.0], rng.uniform(0.0, 1.2, P - 1)])
+            elif kind[i] == 1:
+                d[i] = np.concatenate([[0.5], rng.uniform(-1.5, 0.3, P - 2), [-2.0]]) if P > 1 else [-0.7]
+            else:
+                d[i] = np.concatenate([[-0.3], rng.uniform(-2.0, -0.8, P - 1)])
+        U, _ = np.linalg.qr(rng.standard_normal((N, P, P)) + 1j * rng.standard_normal((N, P, P)))
+        Uh = U.conj().transpose(0, 2, 1)
+        Rxx = (U * d[:, None, :]) @ Uh
+        A = rng.standard_normal((N, P, P)) + 1j * rng.standard_normal((N, P, P))
+        Rnn = A @ A.conj().transpose(0, 2, 1) / P + 0.5 * np.eye(P) + (U * np.maximum(-d, 0.0)[:, None, :]) @ Uh
+        Rxx = Rxx.reshape(2, n, P, P).astype(np.complex64)
+        Rnn = Rnn.reshape(2, n, P, P).astype(np.complex64)
+        for typ in ('mwf', 'r1-mwf'):
+            for mu in (1.0, 0.3):
+                w = eng.mwf_filter(Rxx, Rnn, type=typ, mu=mu).numpy().astype(np.complex128)
+                assert w.shape == (2, n, P)
+                wr = _mwf_variant_ref(Rxx, Rnn, mu, typ)
+                for b, i in ((0, 0), (1, n - 1)):
+                    wi, _ = mo.intern_filter(Rxx[b, i].astype(np.complex128), Rnn[b, i].astype(np.complex128), mu=mu, type=typ)
+                    assert relerr(wi, wr[b, i]) < 1e-9, (P, typ, mu, relerr(wi, wr[b, i]))
+                e = np.linalg.norm(w - wr, axis=-1) / np.linalg.norm(wr, axis=-1)
+                out[(P, typ, mu)] = float(e.max())
+                assert np.all(np.isfinite(w)) and e.max() < tol, (P, typ, mu, kind.reshape(2, n)[np.unravel_index(e.argmax(), e.shape)], e.max())
+    return out
+
+
 def check_solver_routes(make_engine, sizes=(9, 12, 15, 16), n=37, option='solve_dpp'):
     """9 <= P <= 16: the register / DPP solver (option "solve_dpp", csrc/k_solve_dpp.h) -- or, option = 'solve_thread', 5 <= P <= 8: one
     thread per pencil (csrc/k_solve_small.h) -- against the LDS group solver on the same pencils: covariance-like, nearly singular noise (a

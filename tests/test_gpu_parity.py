@@ -190,6 +190,18 @@ def test_solver_degenerate_inputs(make_engine):
     pc.check_solver_degenerate(make_engine)
 
 
+@pytest.mark.parametrize('sizes,option,value', [((1, 2, 3, 4), None, None), ((5, 6, 7, 8), 'solve_thread', 1), ((5, 6, 7, 8), 'solve_thread', 0),
+                                                (tuple(range(9, 17)), 'solve_dpp', 1), (tuple(range(9, 17)), 'solve_dpp', 0)])
+def test_solver_indefinite(make_engine, sizes, option, value):
+    """Indefinite pencils (Rxx = Ryy - Rnn): the top generalized eigenpair, clamped, on every route of the rank-1 solve."""
+    print(pc.check_solver_indefinite(make_engine, sizes=sizes, option=option, value=value))
+
+
+def test_mwf_variants(make_engine):
+    """disco_mwf_filter ('mwf', 'r1-mwf'): every P, full and ragged blocks, mu != 1, PSD / indefinite / negative Rxx."""
+    print(pc.check_mwf_variants(make_engine))
+
+
 @pytest.mark.parametrize('K,M,L,n_fft,staged', [(4, 4, 160000, 512, False), (4, 4, 160000, 512, True), (1, 4, 160000, 512, False),
                                                 (2, 3, 20000, 512, False), (2, 2, 40000, 1024, False), (3, 2, 30000, 512, True),
                                                 (8, 8, 40000, 1024, False)])

@@ -174,6 +174,31 @@ def test_intern_filter_vs_reference_golden(golden_dir):
         intern_filter(R, R + 0.1, type='gevd')
 
 
+@pytest.mark.parametrize('typ', ['gevd', 'r1-mwf'])
+def test_intern_filter_on_speech_minus_noise(typ):
+    """intern_filter(Ryy - Rnn, Rnn, ...), the way a drop-in caller passes the speech statistics: an indefinite Rxx whose top
+    generalized eigenvalue is small and positive while the dominant one is negative (noise over-estimated in most directions)."""
+    from disco_amd.se_utils.internal_formulas import intern_filter
+    rng = np.random.default_rng(37)
+    for P in (2, 4, 7, 15):
+        for trial in range(3):
+            A = rng.standard_normal((P, P)) + 1j * rng.standard_normal((P, P))
+            Rnn = A @ A.conj().T / P + 0.5 * np.eye(P)
+            L = np.linalg.cholesky(Rnn)
+            V, _ = np.linalg.qr(rng.standard_normal((P, P)) + 1j * rng.standard_normal((P, P)))
+            lam = np.concatenate([[1.5], rng.uniform(0.05, 0.9, P - 1)])          # generalized spectrum of (Ryy, Rnn)
+            Ryy = L @ (V * lam) @ V.conj().T @ L.conj().T
+            Rxx = (Ryy - Rnn).astype(np.complex64)
+            Rn = Rnn.astype(np.complex64)
+            assert np.linalg.eigvalsh(Rxx.astype(np.complex128)).min() < 0
+            kw = dict(type='gevd', rank=1) if typ == 'gevd' else dict(type=typ)
+            w, (t1, _) = intern_filter(Rxx, Rn, mu=1, **kw)
+            wr, (t1r, _) = mo.intern_filter(Rxx.astype(np.complex128), Rn.astype(np.complex128), mu=1, **kw)
+            assert relerr(w, wr) < 2e-5, (P, trial, relerr(w, wr))
+            if typ == 'gevd':
+                assert relerr(t1, t1r) < 2e-5, (P, trial, relerr(t1, t1r))
+
+
 def test_tf_mask_vs_reference_golden(golden_dir):
     from disco_amd.dnn.utils import tf_mask
     g = np.load(os.path.join(golden_dir, 'tf_mask_ref.npz'))

@@ -172,6 +172,17 @@ def test_emu_solver_degenerate(make_engine):
     pc.check_solver_degenerate(make_engine)
 
 
+@pytest.mark.parametrize('sizes,option,value', [((1, 2, 3, 4), None, None), ((5, 7, 8), 'solve_thread', 1), ((5, 7, 8), 'solve_thread', 0),
+                                                ((9, 12, 15, 16), 'solve_dpp', 1), ((9, 12, 15, 16), 'solve_dpp', 0)])
+def test_emu_solver_indefinite(make_engine, sizes, option, value):
+    """Indefinite pencils: the top eigenpair, on every route (the plain-statement forms of csrc/k_solve*.h)."""
+    print(pc.check_solver_indefinite(make_engine, sizes=sizes, option=option, value=value, per_case=3))
+
+
+def test_emu_mwf_variants(make_engine):
+    print(pc.check_mwf_variants(make_engine, sizes=(1, 2, 3, 4, 5, 8, 9, 15, 16), n=9))
+
+
 @pytest.mark.parametrize('K,M,L,n_fft,tuning', [(2, 2, 25700, 512, (80, 1, 1, 64)), (3, 2, 13000, 512, (13, 2, 3, 5)),
                                                (2, 2, 9000, 512, (80, 1, 1, 2)), (2, 1, 20000, 1024, (7, 1, 2, 0)),
                                                (1, 3, 25700, 512, (80, 1, 1, 64)), (1, 4, 9000, 512, (9, 1, 1, 4)), (1, 2, 5000, 1024, (3, 1, 1, 2)),
