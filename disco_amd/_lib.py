@@ -63,6 +63,7 @@ PROTOTYPES = {
     'disco_mask_oracle': (_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     'disco_cov_masked': (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     'disco_gevd_mwf_r1': (_int, [_vp, _vp, _vp, _i64, _int, _f, _vp, _vp, _vp]),
+    'disco_gevd_mwf': (_int, [_vp, _vp, _vp, _i64, _int, _int, _f, _vp, _vp, _vp]),
     'disco_mwf_filter': (_int, [_vp, _vp, _vp, _i64, _int, _f, _int, _vp, _vp]),
     'disco_gevd_mwf_r1_pending': (_int, [_vp, _f, _vp, _vp, _vp]),
     'disco_apply': (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),

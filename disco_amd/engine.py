@@ -428,6 +428,20 @@ class Engine:
                                              t1.ptr if want_t1 else None, self.stream))
         return w, t1
 
+    def gevd_mwf(self, Rxx, Rnn, rank, mu=None, want_t1=True):
+        """Rxx, Rnn (..., P, P) -> w, t1 (..., P)   [intern_filter(..., 'gevd', rank), internal_formulas.py:56-73, for a kept rank >= 0;
+        rank >= P is full rank]"""
+        shape = tuple(Rxx.shape)
+        P = shape[-1]
+        n_prob = int(np.prod(shape[:-2], dtype=np.int64))
+        pa, ka = self.to_device(Rxx, np.complex64)
+        pb, kb = self.to_device(Rnn, np.complex64)
+        w = self.empty(shape[:-1], np.complex64)
+        t1 = self.empty(shape[:-1], np.complex64) if want_t1 else None
+        self._chk(self.lib.disco_gevd_mwf(self.ctx, pa, pb, n_prob, P, int(rank), self.cfg.mu if mu is None else mu, w.ptr,
+                                          t1.ptr if want_t1 else None, self.stream))
+        return w, t1
+
     def mwf_filter(self, Rxx, Rnn, type='r1-mwf', mu=None):
         """intern_filter's 'r1-mwf' / 'mwf' branches (internal_formulas.py:45-54, 74-76), batched: (..., P, P) -> w (..., P)."""
         shape = tuple(Rxx.shape)

@@ -2,8 +2,11 @@
 
 All three branches run on the GPU: type='gevd' with rank=1 is the one the hot path uses (tango.py:367, 443); 'r1-mwf'
 (the function's default type, internal_formulas.py:45-54) and 'mwf' (:74-76) are dead there and offered for
-completeness (disco_mwf_filter).  An unknown type raises AttributeError and type='gevd' with the default rank='Full'
-raises TypeError, exactly like the reference."""
+completeness (disco_mwf_filter).  type='gevd' with any other integer rank -- the low-rank GEVD-MWF of Serizel et al. 2014 --
+runs the full generalized eigendecomposition (disco_gevd_mwf): the rank is mapped to a kept count by the reference's slicing
+rule `D[rank:, :] = 0` (rank >= P: full rank; rank < 0: max(P + rank, 0) kept), and mu = 0 with fewer than P pairs kept raises
+numpy.linalg.LinAlgError, as the reference's inv(D + 0 I) does.  An unknown type raises AttributeError and type='gevd' with the
+default rank='Full' raises TypeError, exactly like the reference ('full' raises TypeError too, see tests/test_reference_surface_cpu.py)."""
 import numpy as np
 
 from .._engines import get_engine
@@ -36,20 +39,35 @@ def intern_filter(Rxx, Rnn, mu=1, type='r1-mwf', rank='Full'):
         raise AttributeError('Unknown filter reference')                      # internal_formulas.py:79
     if not isinstance(rank, (int, np.integer)):
         raise TypeError("slice indices must be integers (rank='Full' is unusable with type='gevd', as in the reference)")
-    if int(rank) != 1:
-        raise NotImplementedError('intern_filter: only rank=1 runs on the GPU')
     Rxx = np.ascontiguousarray(Rxx, dtype=np.complex64)
     Rnn = np.ascontiguousarray(Rnn, dtype=np.complex64)
     assert Rxx.shape == Rnn.shape and Rxx.ndim == 2 and Rxx.shape[0] == Rxx.shape[1]
-    eng = get_engine(rooms=1, nodes=1, mics=1, length=1024)
-    w, t1 = eng.gevd_mwf_r1(Rxx[None], Rnn[None], mu=float(mu))
-    return w.numpy()[0].astype(np.complex128), (t1.numpy()[0].astype(np.complex128), np.arange(Rxx.shape[0], dtype=np.int64))
+    w, t1 = _gevd(Rxx[None], Rnn[None], mu, int(rank))
+    return w[0].astype(np.complex128), (t1[0].astype(np.complex128), np.arange(Rxx.shape[0], dtype=np.int64))
 
 
-def intern_filter_batched(Rxx, Rnn, mu=1):
-    """(..., P, P) pencils -> w, t1 (..., P): the batched form the engine actually runs."""
+def kept_rank(rank, P):
+    """How many generalized eigenpairs the reference's `D[rank:, :] = 0` keeps of P (Python slicing)."""
+    return len(range(P)[:int(rank)])
+
+
+def _gevd(Rxx, Rnn, mu, rank):
+    """(..., P, P) complex64 pencils -> w, t1 (..., P) complex64; rank 1 keeps its own solver (disco_gevd_mwf_r1)."""
+    if rank == 1:
+        w, t1 = get_engine(rooms=1, nodes=1, mics=1, length=1024).gevd_mwf_r1(Rxx, Rnn, mu=float(mu))
+        return w.numpy(), t1.numpy()
+    P = Rxx.shape[-1]
+    r = kept_rank(rank, P)
+    if float(mu) == 0.0 and r < P:
+        raise np.linalg.LinAlgError('Singular matrix')                        # inv(D + 0 I) with a dropped pair, as in the reference
+    w, t1 = get_engine(rooms=1, nodes=1, mics=1, length=1024).gevd_mwf(Rxx, Rnn, r, mu=float(mu))
+    return w.numpy(), t1.numpy()
+
+
+def intern_filter_batched(Rxx, Rnn, mu=1, rank=1):
+    """(..., P, P) pencils -> w, t1 (..., P): the batched form the engine actually runs.  rank: any integer, as in intern_filter."""
+    if not isinstance(rank, (int, np.integer)):
+        raise TypeError('rank must be an integer')
     Rxx = np.ascontiguousarray(Rxx, dtype=np.complex64)
     Rnn = np.ascontiguousarray(Rnn, dtype=np.complex64)
-    eng = get_engine(rooms=1, nodes=1, mics=1, length=1024)
-    w, t1 = eng.gevd_mwf_r1(Rxx, Rnn, mu=float(mu))
-    return w.numpy(), t1.numpy()
+    return _gevd(Rxx, Rnn, mu, int(rank))

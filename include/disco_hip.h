@@ -221,6 +221,21 @@ int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float* mask,
 int disco_gevd_mwf_r1(disco_ctx* ctx, const disco_c32* Rss, const disco_c32* Rnn, int64_t n_prob, int P,
                       float mu, disco_c32* w, disco_c32* t1, disco_stream s);
 
+/* intern_filter(Rxx, Rnn, mu, type='gevd', rank) for every kept rank -- internal_formulas.py:56-73, batched.
+ * With Rnn = L L^H and C = L^-1 Rxx L^-H = V diag(d) V^H (float64 Cholesky whitening, then every eigenpair of C by cyclic complex
+ * Jacobi in float64):
+ *     w  = L00 L^-H sum_{i kept} f_i v_i conj(v_i[0]),   f_i = dc_i / (dc_i + mu),  dc_i = d_i clamped to [eps, 1e6]
+ *     t1 = L00 L^-H v_top conj(v_top[0])   (the rank-1 t1, whatever the rank)
+ * The pairs are ranked by their UNCLAMPED eigenvalue, descending, ties broken by index; the first min(rank, P) are kept.  rank >= P is
+ * full rank, rank = 0 gives w = 0; a negative rank is DISCO_E_ARG (the reference's slicing rule, r = max(P + rank, 0), is the caller's).
+ * mu = 0 with rank < P is the reference's singular inv(D + 0 I); here the dropped pairs simply contribute nothing.
+ * A numerically singular Rnn takes the pivot floor of the rank-1 solver (its breakdown columns are zeroed): finite and bounded, with
+ * the large eigenvalues it produces clamped to 1e6.  A pencil that is not finite returns non-finite w, t1 and leaves the other
+ * pencils of the batch unchanged.
+ * Rxx, Rnn: [n_prob][P][P] (Hermitian)  ->  w, t1: [n_prob][P]  (t1 may be NULL).  1 <= P <= 16. */
+int disco_gevd_mwf(disco_ctx* ctx, const disco_c32* Rxx, const disco_c32* Rnn, int64_t n_prob, int P, int rank, float mu,
+                   disco_c32* w, disco_c32* t1, disco_stream s);
+
 /* intern_filter's other two branches (internal_formulas.py:45-54 'r1-mwf' -- the function's DEFAULT type -- and :74-76 'mwf');
  * neither is reached by offline_tango, both are here so that the whole function is:
  *   DISCO_FILTER_R1_MWF  Rxx1 = |Dmax| x x^H (top eigenpair of Rxx: Dmax its largest eigenvalue, as D.max());
