@@ -14,7 +14,8 @@ extern "C" int disco_apply(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
     if (!X || !w || !out) return fail(ctx, DISCO_E_ARG, "disco_apply: null argument");
     if (KR != 0 && KR != c.nodes - 1) return fail(ctx, DISCO_E_ARG, "disco_apply: P must be M or M + K - 1");
     if (KR > 0 && !Z) return fail(ctx, DISCO_E_ARG, "disco_apply: Z required when P > M");
-    if (P > CB_PMAX) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_apply: P > 16 not supported");
+    if (M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_apply: more than 8 mics per node");
+    if (P > 32) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_apply: P = M + K - 1 > 32 not supported");
     const long long G = (long long)c.rooms * ctx->Kl;
     const long long TF = (long long)ctx->T * ctx->F;
     int bpn = (int)std::min<long long>((TF + 255) / 256, 64);
@@ -40,7 +41,7 @@ extern "C" int disco_apply(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
         while (G * tiles * t_chunks > 0x7ffffff0LL && t_chunks > 1) t_chunks >>= 1;
         const long long items_m = G * tiles * t_chunks;
         const dim3 grid_m((unsigned)((items_m + DISCO_APPLY_XCD - 1) / DISCO_APPLY_XCD * DISCO_APPLY_XCD));      // ids are dealt over the XCDs
-        if ((M == 4 || M == 8) && KR >= 1) {        // contiguous granule loads through a wave-private LDS tile (k_apply_mq)
+        if ((M == 4 || M == 8) && KR >= 1 && KR <= 15) {        // contiguous granule loads through a wave-private LDS tile (k_apply_mq)
             const int krt = KR <= 1 ? 1 : (KR <= 3 ? 3 : (KR <= 7 ? 7 : 15));
 #define Q_(M_, KRT_)                                                                                                                  \
     if (M == M_ && krt == KRT_)                                                                                                       \
@@ -50,6 +51,19 @@ extern "C" int disco_apply(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
             Q_(4, 1) Q_(4, 3) Q_(4, 7) Q_(4, 15) Q_(8, 1) Q_(8, 3) Q_(8, 7) Q_(8, 15)
 #undef Q_
             return check_launch(ctx, "k_apply_mq");
+        }
+        if (KR > 15) {                              // wide networks (P > 16 with more than 15 remote rows)
+            switch (M) {
+#define C_(M_)                                                                                                          \
+    case M_:                                                                                                            \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_m<M_, 31>), grid_m, dim3(64), 0, (hipStream_t)s, (const c32*)X, (const c32*)Z, \
+                           (const c32*)w, (c32*)out, KR, c.nodes, ctx->T, ctx->F, conj_w, tiles, t_chunks, ctx->Kl, ctx->k0, ctx->zblk, \
+                           (long long)c.rooms);                                                                    \
+        break;
+                C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8)
+#undef C_
+            }
+            return check_launch(ctx, "k_apply_m");
         }
         switch (M) {
 #define C_(M_)                                                                                                          \

@@ -1,6 +1,7 @@
 // libdisco_hip.so -- host side of the C ABI declared in include/disco_hip.h (gfx950 only): masked covariances (staged form)
 #include "host.h"
 #include "k_cov.h"
+#include "k_cov_wide.h"
 
 using namespace disco;
 using namespace disco_host;
@@ -74,6 +75,60 @@ int cov_finalize(disco_ctx* ctx, int chunks, int P, disco_c32* Rss, disco_c32* R
                        1.0f / (float)ctx->T);
     return check_launch(ctx, "k_cov_finalize");
 }
+// 17 <= P <= 32 (k_cov_wide.h): always the full triangle into `scratch` (the step-1 sums are not re-used: no skiploc)
+static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn,
+                             int mask_remote, int P, int* chunks_out, disco_stream s) {
+    const disco_cfg& c = ctx->cfg;
+    const int M = c.mics, KR = P - M;
+    const int chunks = cov_chunks(ctx);
+    const long long G = (long long)c.rooms * ctx->Kl;
+    const int NP = P * (P + 1) / 2, tiles = (ctx->F - 1 + 63) / 64;
+    const int nbg = (cov_wide_blocks(P) + CW_WAVES - 1) / CW_WAVES;
+    const long long n_items = G * (tiles + 1) * chunks * nbg;
+    const long long grid = (n_items + DISCO_COV_WIDE_XCD - 1) / DISCO_COV_WIDE_XCD * DISCO_COV_WIDE_XCD;
+    if (grid > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: batch too large (P > 16: more than 2^31 workgroups)");
+    // the scratch this batch needs, G x chunks x F x NP x 16 B, checked before anything runs
+    const size_t need = (size_t)G * chunks * ctx->F * NP * sizeof(float4);
+    if (ctx->scratch_bytes < need) {
+        int rc = ensure_scratch(ctx, need);
+        if (rc) {
+            (void)hipGetLastError();
+            char m[400];
+            snprintf(m, sizeof(m), "disco_cov_masked: P = %d needs %.2f GiB of partial-sum scratch (%lld units x %d chunks x %d bins x %d pairs "
+                     "x 16 B), which the device cannot provide: split the batch into fewer rooms", P, need / 1073741824.0, G, chunks, ctx->F, NP);
+            return fail(ctx, DISCO_E_UNSUPPORTED, m);
+        }
+    }
+    CovArgs a;
+    a.X = (const c32*)X;
+    a.mask = mask;
+    a.Zs = (const c32*)Zs;
+    a.Zn = (const c32*)Zn;
+    a.part = (float4*)ctx->scratch;
+    a.K = c.nodes;
+    a.T = ctx->T;
+    a.F = ctx->F;
+    a.chunks = chunks;
+    a.mask_remote = mask_remote;
+    a.Kl = ctx->Kl;
+    a.k0 = ctx->k0;
+    a.zblk = ctx->zblk;
+    a.R = c.rooms;
+    if (Zs == Zn)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<true>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<false>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
+    *chunks_out = chunks;
+    ctx->pending_chunks = chunks;
+    ctx->pending_P = P;
+    ctx->pending_skiploc = 0;
+    ctx->loc_M = 0;                              // `scratch` no longer holds step-1 sums
+    ctx->loc_chunks = chunks;
+    ctx->loc_X = X;
+    ctx->loc_mask = mask;
+    return check_launch(ctx, "k_cov_wide");
+}
+
 // (M, KR) shapes of the block-partitioned kernels k_cov_split / k_cov_split_lds (api_cov_split.hip)
 bool cov_split_shape(int M, int KR);
 bool launch_cov_split_shape(int M, int KR, bool skiploc, int sub, unsigned nblk, hipStream_t st, const disco::CovArgs& a);
@@ -88,7 +143,9 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
     if (!X || !mask) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: null argument");
     if (KR != 0 && KR != c.nodes - 1) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: P must be M or M + K - 1");
     if (KR > 0 && (!Zs || !Zn)) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: Zs/Zn required when P > M");
-    if (P > CB_PMAX || M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: P > 16 or M > 8");
+    if (M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: M > 8 mics per node not supported");
+    if (P > CW_PMAX) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: P = M + K - 1 > 32 not supported");
+    if (P > CB_PMAX) return cov_partials_wide(ctx, X, mask, Zs, Zn, mask_remote, P, chunks_out, s);
     int chunks = cov_chunks(ctx);
     const long long G = (long long)c.rooms * ctx->Kl;
     const int NP = P * (P + 1) / 2;

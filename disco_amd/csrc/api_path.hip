@@ -4,6 +4,7 @@
 #include <functional>
 #include "k_apply.h"
 #include "k_cov.h"
+#include "k_cov_wide.h"
 #include "k_stft.h"
 
 using namespace disco;
@@ -139,7 +140,21 @@ int acquire_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, const Ws
 int reserve_scratch(disco_ctx* ctx) {
     const disco_cfg& c = ctx->cfg;
     const size_t G = (size_t)c.rooms * ctx->Kl;
-    const size_t P = (size_t)std::min(c.mics + c.nodes - 1, 16);
+    const int P2 = c.mics + c.nodes - 1;
+    if (P2 > CB_PMAX && P2 <= CW_PMAX && c.mics <= 8) {
+        // 17 <= P <= 32: step 1 (P = M, the chunk counts below) and step 2 (k_cov_wide, cov_chunks) size `scratch`; `scratch2` only
+        // ever holds re-used step-1 sums, which the wide route does not take
+        const size_t NP1 = (size_t)c.mics * (c.mics + 1) / 2, NP2 = (size_t)P2 * (P2 + 1) / 2;
+        int ch1 = cov_chunks(ctx);
+        if (c.mics >= 7) ch1 = std::max(ch1, 2 * cov1_f64_chunks(ctx));
+        ch1 = std::max(ch1, stft_cov_chunks(ctx, nullptr));
+        const size_t need1 = G * (size_t)ch1 * ctx->F * NP1 * sizeof(float4);
+        const size_t need2 = G * (size_t)cov_chunks(ctx) * ctx->F * NP2 * sizeof(float4);
+        int rc = ensure_scratch(ctx, std::max(need1, need2));
+        if (!rc) rc = ensure_scratch2(ctx, need1);
+        return rc;
+    }
+    const size_t P = (size_t)std::min(P2, 16);
     const size_t NP = P * (P + 1) / 2;
     int chunks = std::max(cov_chunks(ctx), step2_chunks(ctx, (ctx->F - 1) / 64 + 1));
     if (c.mics >= 7) chunks = std::max(chunks, 2 * cov1_f64_chunks(ctx));                       // the (hi, lo) pairs of k_cov_loc_f64
@@ -329,7 +344,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
     const disco_cfg& c = ctx->cfg;
     if (c.mask_type < DISCO_MASK_IRM || c.mask_type > DISCO_MASK_IAM) return fail(ctx, DISCO_E_ARG, "disco_tango_reference: unknown mask type");
     const int M = c.mics, K = c.nodes, P2 = M + K - 1;
-    if (P2 > CB_PMAX || M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_tango_reference: M + K - 1 > 16 or M > 8");
+    if (P2 > CW_PMAX || M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_tango_reference: M + K - 1 > 32 or M > 8 not supported");
     // the workspace: the caller's, or a context-owned one kept in `own_ws` (shared with the enhanced-output entry points)
     const RefLayout l = ref_layout(ctx);
     char* ws = (char*)workspace;

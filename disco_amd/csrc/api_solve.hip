@@ -2,6 +2,7 @@
 #include "host.h"
 #include "k_solve.h"
 #include "k_solve_small.h"
+#include "k_solve_wide.h"
 
 using namespace disco;
 using namespace disco_host;
@@ -40,9 +41,20 @@ static void launch_solve(const SolveSrc& src, long long n_prob, double mu, c32* 
 
 static int solve_dispatch(disco_ctx* ctx, const SolveSrc& src, int64_t n_prob, int P, float mu, disco_c32* w, disco_c32* t1,
                           disco_stream s) {
-    if (P < 1 || P > 16) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_gevd_mwf_r1: P must be in 1..16");
+    if (P < 1 || P > SW_PMAX) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_gevd_mwf_r1: P must be in 1..32");
     if (n_prob / 4 > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_gevd_mwf_r1: batch too large");
     hipStream_t st = (hipStream_t)s;
+    if (P >= SW_PMIN) {                          // 17 <= P <= 32: one wave per pencil (k_solve_wide.h)
+        if (n_prob > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_gevd_mwf_r1: batch too large (P > 16: at most 2^31 - 1 pencils)");
+        if (src.part_loc) return fail(ctx, DISCO_E_ARG, "disco_gevd_mwf_r1: P > 16 takes no re-used step-1 block");
+        if (src.part)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gevd_mwf_r1_wide<true>), dim3((unsigned)n_prob), dim3(64), 0, st, src, (long long)n_prob, P,
+                               (double)mu, (c32*)w, (c32*)t1);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gevd_mwf_r1_wide<false>), dim3((unsigned)n_prob), dim3(64), 0, st, src, (long long)n_prob, P,
+                               (double)mu, (c32*)w, (c32*)t1);
+        return check_launch(ctx, "k_gevd_mwf_r1_wide");
+    }
     if (P >= 9 && ctx->opt[DISCO_OPT_SOLVE_DPP] != 0) {
         launch_solve_dpp(P, src, n_prob, (double)mu, (c32*)w, (c32*)t1, st);
         return check_launch(ctx, "k_gevd_mwf_r1_dpp");

@@ -51,7 +51,8 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(256) void k_apply(const c32* __r
 #ifndef DISCO_APPLY_XCD
 #define DISCO_APPLY_XCD 8             // XCDs the workgroup ids of k_apply_m are dealt over
 #endif
-template <int M>
+// KRMAX: the remote rows the loop is unrolled for (15: P <= 16 with M >= 1 ... ; 31: the wide networks, 17 <= P <= 32)
+template <int M, int KRMAX = 15>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64) void k_apply_m(const c32* __restrict__ X, const c32* __restrict__ Z,
                                                  const c32* __restrict__ w, c32* __restrict__ out, int KR,
                                                  int K, int T, int F, int conj_w, int tiles, int t_chunks, int Kl, int k0, int zblk,
@@ -80,11 +81,11 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64) void k_apply_m(const c32* __
     const long long TF = (long long)T * F;
     const float sgn = conj_w ? -1.f : 1.f;
     const c32* wf = w + (g * F + f) * (long long)P;
-    c32 wl[M], wr[15];
+    c32 wl[M], wr[KRMAX];
 #pragma unroll
     for (int i = 0; i < M; ++i) wl[i] = make_float2(wf[i].x, sgn * wf[i].y);
 #pragma unroll
-    for (int jj = 0; jj < 15; ++jj) wr[jj] = jj < KR ? make_float2(wf[M + jj].x, sgn * wf[M + jj].y) : make_float2(0.f, 0.f);
+    for (int jj = 0; jj < KRMAX; ++jj) wr[jj] = jj < KR ? make_float2(wf[M + jj].x, sgn * wf[M + jj].y) : make_float2(0.f, 0.f);
 
     for (int t = t0; t < t1; ++t) {
         const long long tf = (long long)t * F + f;
@@ -99,7 +100,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64) void k_apply_m(const c32* __
             ai = fmaf(wl[i].x, x[i].y, fmaf(wl[i].y, x[i].x, ai));
         }
 #pragma unroll
-        for (int jj = 0; jj < 15; ++jj) {
+        for (int jj = 0; jj < KRMAX; ++jj) {
             if (jj < KR) {
                 const int j = jj < k ? jj : jj + 1;
                 const c32 z = Z[z_plane(r, j, K, R, zblk) * TF + tf];

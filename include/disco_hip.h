@@ -207,7 +207,9 @@ int disco_mask_oracle(disco_ctx* ctx, const float* s_ref, const float* n_ref, in
  *   v_n(t,f) = [(1-m)*X_k ; g_n*Zn_j ...               ],   Rnn[f] = mean_t v_n v_n^H
  * with g_s = m, g_n = 1-m when mask_remote != 0 (mask_for_z='local', tango.py:416-418) and 1 otherwise.
  * X [R][K][T][F][M], mask [R][K][T][F], Zs/Zn [R][K][T][F] (row order = concatenate_signals, tango.py:142-155).
- * Rss, Rnn: disco_c32 [R][K][F][P][P]. */
+ * Rss, Rnn: disco_c32 [R][K][F][P][P].  Limits: M <= 8, P <= 32 (DISCO_E_UNSUPPORTED beyond, naming the limit).  17 <= P <= 32
+ * (csrc/k_cov_wide.h) checks the scratch its partial sums need, G x chunks x F x P(P+1)/2 x 16 B, before it runs and refuses a batch
+ * that does not fit with DISCO_E_UNSUPPORTED. */
 int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float* mask,
                      const disco_c32* Zs, const disco_c32* Zn, int mask_remote, int P,
                      disco_c32* Rss, disco_c32* Rnn, disco_stream s);
@@ -217,7 +219,8 @@ int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float* mask,
  * matrix (Ryy - Rnn included): float64 Cholesky whitening + repeated squaring, solved again on a shifted matrix where Rxx
  * is indefinite.  Eigenvalue clamped to [eps, 1e6], w = q d/(d+mu) (Q^-1)[0,0], t1 = q (Q^-1)[0,0]; where every
  * eigenvalue is <= 0, d = eps and w ~ 0.  An exactly repeated top eigenvalue yields some vector of its eigenspace.
- * Rss, Rnn: [n_prob][P][P]  ->  w, t1: [n_prob][P]  (t1 may be NULL).  1 <= P <= 16. */
+ * Rss, Rnn: [n_prob][P][P]  ->  w, t1: [n_prob][P]  (t1 may be NULL).  1 <= P <= 32 (17 <= P <= 32: one wave per pencil,
+ * csrc/k_solve_wide.h, the same algorithm and guards). */
 int disco_gevd_mwf_r1(disco_ctx* ctx, const disco_c32* Rss, const disco_c32* Rnn, int64_t n_prob, int P,
                       float mu, disco_c32* w, disco_c32* t1, disco_stream s);
 
@@ -232,7 +235,7 @@ int disco_gevd_mwf_r1(disco_ctx* ctx, const disco_c32* Rss, const disco_c32* Rnn
  * A numerically singular Rnn takes the pivot floor of the rank-1 solver (its breakdown columns are zeroed): finite and bounded, with
  * the large eigenvalues it produces clamped to 1e6.  A pencil that is not finite returns non-finite w, t1 and leaves the other
  * pencils of the batch unchanged.
- * Rxx, Rnn: [n_prob][P][P] (Hermitian)  ->  w, t1: [n_prob][P]  (t1 may be NULL).  1 <= P <= 16. */
+ * Rxx, Rnn: [n_prob][P][P] (Hermitian)  ->  w, t1: [n_prob][P]  (t1 may be NULL).  1 <= P <= 16 (rank 1 above 16: disco_gevd_mwf_r1). */
 int disco_gevd_mwf(disco_ctx* ctx, const disco_c32* Rxx, const disco_c32* Rnn, int64_t n_prob, int P, int rank, float mu,
                    disco_c32* w, disco_c32* t1, disco_stream s);
 
@@ -250,12 +253,12 @@ int disco_mwf_filter(disco_ctx* ctx, const disco_c32* Rxx, const disco_c32* Rnn,
 /* The same solve, fed straight from the partial sums the LAST covariance call of this context left in its scratch
  * (any of disco_cov_masked / disco_stft_cov_fused / disco_step2_cov_fused; those accept Rss == Rnn == NULL when the
  * matrices themselves are not wanted).  Saves writing and re-reading the [R][K][F][P][P] matrices.
- * w, t1: [R][K][F][P] with the P of that covariance call. */
+ * w, t1: [R][K][F][P] with the P of that covariance call (P <= 32). */
 int disco_gevd_mwf_r1_pending(disco_ctx* ctx, float mu, disco_c32* w, disco_c32* t1, disco_stream s);
 
 /* Filter-and-sum -- the np.inner loops tango.py:369-374 / 445-450:
  *   out[t,f] = sum_p c(w[f,p]) * v[p,t,f],  v = [X_k ; Z_j (j<k) ; Z_j (j>k)],  c = conj if conj_w else identity.
- * X [R][K][T][F][M]; Z [R][K][T][F] or NULL when P == M; w [R][K][F][P]; out [R][K][T][F]. */
+ * X [R][K][T][F][M]; Z [R][K][T][F] or NULL when P == M; w [R][K][F][P]; out [R][K][T][F].  M <= 8, P <= 32. */
 int disco_apply(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, const disco_c32* w, int P,
                 int conj_w, disco_c32* out, disco_stream s);
 
@@ -359,7 +362,7 @@ int disco_tango_reference(disco_ctx* ctx, const float* y, const float* s, const 
 /* DANSE-style continuation of the two-step scheme (BASELINE.json configs[4]; NOT in the reference, which is strictly
  * two-step, tango.py:1-7): step 2 is run `iters` times, and between two runs every node re-compresses with the local part
  * of its new global filter, z_k <- w_glo,k[0:M]^H y_k.  iters = 1 gives exactly disco_tango_enhance's outputs.  Staged
- * kernels (z materialised), any P = M + K - 1 <= 16.  Arguments as disco_tango_enhance; z_y returns the LAST z. */
+ * kernels (z materialised), any P = M + K - 1 <= 32.  Arguments as disco_tango_enhance; z_y returns the LAST z. */
 int disco_tango_enhance_iterated(disco_ctx* ctx, const float* y, const float* mask_z, const float* mask_w, int iters,
                                  float* out, disco_c32* z_y, disco_c32* yf,
                                  void* workspace, size_t workspace_bytes, disco_stream s);
