@@ -11,10 +11,12 @@ One "step" = the whole path over the whole batch: oracle mask (2 STFTs/node) -> 
 exchange -> covariance -> solve -> filter -> iSTFT, inputs and outputs resident in HBM.  metric = node-frames/s (1 node-frame =
 one hop of all M mics of one node); x real-time = audio seconds per room / seconds per step.
 
-The plain command (`python bench.py [--gpus N]`, headline C3) ALSO runs the other BASELINE configurations for a few steps each
--- C5, C2 (256 and 4000 rooms), C4 and the online mode -- and attaches them as `"configs": {name: {ms_per_step, value, roofline,
-parity_sample, stages, ...}}` inside the same JSON line (`--extras none` skips them, `--extras C5,C2` picks).  The headline
-fields are untouched by them: they run after the headline's timed region.
+The plain command (`python bench.py [--gpus N] [--steps K] [--warmup W]`) does only what the headline figure needs: it sets up,
+warms up, times the steps, writes --dump-outputs and prints the line (`roofline`, `cpu_baseline` and `parity_sample` absent or null).
+`--full` adds, after the headline's timed region: the sampled-room oracle check, the per-stage timing pass behind `roofline` and
+`stages`, the CPU baseline and -- for the plain C3 headline -- the other BASELINE configurations for a few steps each (C5, C2 at 256
+and 4000 rooms, C4 and the online mode), attached as `"configs": {name: {ms_per_step, value, roofline, parity_sample, stages, ...}}`
+(`--extras none` skips them, `--extras C5,C2` picks).  The headline fields are untouched by any of it.
 
 Multi-GPU (`--gpus N`): one process per GPU.  Under torch.distributed.run (RANK/WORLD_SIZE in the environment) the ranks are
 taken as given; started plainly with --gpus N > 1 the script launches its own N ranks (disco_amd/dist.py:launch_ranks).
@@ -23,7 +25,7 @@ taken as given; started plainly with --gpus N > 1 the script launches its own N 
   --shard nodes          : the nodes of every room are split over the ranks and z is exchanged with one RCCL all-gather per
                            step-2 iteration -- the exchange DISCO's algorithm performs (tango.py:378-386); the line then carries
                            the all-gather's bytes per rank and link rate.
-EVERY rank checks sampled rooms of ITS OWN batch -- the output of the last timed step -- against the float64 CPU oracle
+With --full, EVERY rank checks sampled rooms of ITS OWN batch -- the output of the last timed step -- against the float64 CPU oracle
 ("parity_sample": rank 0's rooms in `per_room`, every rank's rooms / device / worst error in `ranks`, the worst over all
 ranks in `worst_rel_all_ranks`); a failure on any rank exits non-zero after the line is printed.  The oracle runs in worker
 processes while the GPU goes on with the next workload.
@@ -57,7 +59,7 @@ CONFIGS = {
     'C4': dict(rooms=125, nodes=4, mics=4, n_fft=512, iters=1, mask='crnn', online_every=0),
     'C5': dict(rooms=200, nodes=8, mics=8, n_fft=1024, iters=2, mask='oracle', online_every=0),
 }
-# what the plain command runs after the headline (name -> workload, steps, warmup, rooms rank 0 checks against the oracle)
+# what --full runs after the plain C3 headline (name -> workload, steps, warmup, rooms rank 0 checks against the oracle)
 EXTRAS = {
     # (the launch-bound C2 first, right behind the headline: a 0.9 ms step does not survive the host being shared with the oracle
     # workers of a wide-shape workload -- 2.8 instead of 0.87 ms behind C5's three 8 x 8 rooms)
@@ -408,14 +410,18 @@ def parse_args(argv=None):
     ap.add_argument('--graph', action='store_true',
                     help='capture one step (mask + whole path) into a hipGraph on a side stream and time its replays: one launch per '
                          'step instead of 6-20 (matters for small batches; oracle masks, room-sharded batch path only)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the sampled-room oracle check, the per-stage timing pass '
+                         '(roofline, stages; the online stream), the CPU baseline and the other BASELINE configurations (--extras). '
+                         'Without it the command sets up, warms up, times the steps, writes --dump-outputs and prints the line')
     ap.add_argument('--extras', default='auto',
-                    help="the other BASELINE configurations run after the headline and attached as `configs`: 'auto' (all of "
+                    help="--full: the other BASELINE configurations run after the headline and attached as `configs`: 'auto' (all of "
                          f"{', '.join(EXTRAS)} when the command is the plain C3 headline, none otherwise), 'all', 'none', or a comma list")
     ap.add_argument('--tuning', default=None, help='disco_set_tuning values a,b,c,d for the headline workload (experiments)')
     ap.add_argument('--detail', default=None, help='where the full result goes (default: bench_detail.json at the repo root, and gpurun_out/ when present); stdout carries the compact line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-stage-timing', action='store_true')
-    ap.add_argument('--no-parity', action='store_true', help='skip the sampled-room oracle check after the timed region')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-stage-timing', action='store_true', help='--full without the per-stage timing pass')
+    ap.add_argument('--no-parity', action='store_true', help='--full without the sampled-room oracle check after the timed region')
     ap.add_argument('--parity-rooms', type=int, default=6)
     ap.add_argument('--parity-workers', type=int, default=8, help='oracle worker processes per rank (sweeps of whole batches: raise it on a many-core host)')
     ap.add_argument('--pmc-calibrate', action='store_true', help='also run a 4 GiB device copy (known bytes) for PMC calibration')
@@ -438,6 +444,11 @@ def parse_args(argv=None):
     for k in ('rooms', 'nodes', 'mics', 'n_fft', 'iters', 'mask', 'online_every'):
         if getattr(args, k) is None:
             setattr(args, k, cfg[k])
+    if not args.full:
+        if args.extras not in ('auto', 'none'):
+            ap.error('--extras: the other configurations run with --full')
+        args.extras = 'none'
+        args.no_cpu_baseline = args.no_stage_timing = args.no_parity = True
     if args.extras == 'auto':
         args.extras = 'all' if (plain and args.config == 'C3' and args.shard == 'rooms' and not args.graph and args.length == 160000) else 'none'
     if args.extras == 'all':
@@ -656,11 +667,12 @@ def run_workload(name, w, steps, warmup, env, headline, n_parity_rank0, args):
     finite = bool(torch.isfinite(out).all())
     if node_sharded and args.overlap_exchange:
         # an event pair around an OVERLAPPED gather also spans the other half-batch's kernels (round-5 ADVICE): the exchange is timed in its
-        # own pass after the timed region, whole batch per gather, nothing beside it
-        for _ in range(min(steps, 3)):
-            eng._chk(lib.disco_mask_oracle(eng.ctx, s_ref.data_ptr(), n_ref.data_ptr(), G, mask.data_ptr(), None))
-            ns.tango_enhance_node_sharded_torch(eng, y, mask, mask, iters=iters, out=out, want_yf=False, overlap=False, gather_events=gather_events)
-        torch.cuda.synchronize()
+        # own pass after the timed region, whole batch per gather, nothing beside it (--full)
+        if args.full:
+            for _ in range(min(steps, 3)):
+                eng._chk(lib.disco_mask_oracle(eng.ctx, s_ref.data_ptr(), n_ref.data_ptr(), G, mask.data_ptr(), None))
+                ns.tango_enhance_node_sharded_torch(eng, y, mask, mask, iters=iters, out=out, want_yf=False, overlap=False, gather_events=gather_events)
+            torch.cuda.synchronize()
         gather_ms = [a_.elapsed_time(b_) for a_, b_ in gather_events]
     else:
         gather_ms = [a_.elapsed_time(b_) for a_, b_ in gather_events[-steps * iters:]] if gather_events else []
@@ -822,7 +834,8 @@ def run_workload(name, w, steps, warmup, env, headline, n_parity_rank0, args):
     exchange = None
     if node_sharded:
         exchange = exchange_object(R, K, Kl, T, F, iters, gather_ms, world, args.overlap_exchange,
-                                   'separate pass after the timed region, overlap off: whole batch per gather' if args.overlap_exchange
+                                   ('separate pass after the timed region, overlap off: whole batch per gather' if args.full
+                                    else 'not timed: overlapped gathers are timed in a separate pass (--full)') if args.overlap_exchange
                                    else 'inside the timed region: one whole-batch gather per step-2 iteration')
 
     mask_error = None

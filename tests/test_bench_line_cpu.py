@@ -138,3 +138,31 @@ def test_dump_outputs_fixed_sample_within_budget(tmp_path):
     assert bench.parse_args(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path)
     with pytest.raises(SystemExit):
         bench.parse_args(['--steps', '0'])
+
+
+def test_plain_run_times_the_headline_only():
+    """Without --full the command times the headline and nothing else: no oracle check, no per-stage pass, no CPU baseline and no other
+    configuration (an explicit --extras asks for --full), and its line is the compact line of that result.  --full runs all of it."""
+    import pytest
+    import bench
+    for argv in ([], ['--config', 'C5'], ['--shard', 'nodes'], ['--extras', 'none']):
+        a = bench.parse_args(argv)
+        assert not a.full and a.extra_names == [] and a.no_parity and a.no_cpu_baseline and a.no_stage_timing, argv
+    a = bench.parse_args(['--full'])
+    assert a.extra_names == [n for n in bench.EXTRAS if n != 'C4_bf16'] and not (a.no_parity or a.no_cpu_baseline or a.no_stage_timing)
+    assert bench.parse_args(['--full', '--config', 'C5']).extra_names == []
+    assert bench.parse_args(['--full', '--extras', 'C2,C4_bf16', '--no-parity']).extra_names == ['C2', 'C4_bf16']
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--extras', 'C2'])
+    # what main() assembles from a plain run: the headline's own fields, nothing measured beside them
+    d = _line()
+    plain = {k: d[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                               'vs_baseline', 'dtype', 'data', 'x_realtime', 'config')}
+    plain.update(roofline=None, cpu_baseline=None, parity_sample=None, stages=None)
+    plain['summary'] = bench.summary_rows('C3', plain, None, {})
+    line = bench.compact_line(plain)
+    assert list(line)[:12] == ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
+                               'dtype', 'data']
+    assert all(line[k] == d[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'higher_is_better', 'dtype'))
+    assert line['roofline'] is None and line['cpu_baseline'] is None and 'parity_sample' not in line and list(line)[-1] == 'summary'
+    assert line['summary']['C3'][:2] == [round(d['ms_per_step'], 3), round(d['x_realtime'], 1)]

@@ -41,13 +41,13 @@ def _bench_process(args, timeout=600):
 
 
 def _run_bench(args, timeout=600):
-    """-> the FULL result (the side file `--detail` names), after checking the ONE compact stdout line against it."""
+    """-> the FULL result (the side file `--detail` names) of `bench.py --full args`, after checking the ONE compact stdout line against it."""
     import json
     import os
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         detail = os.path.join(td, 'detail.json')
-        p = _bench_process(args + ['--detail', detail], timeout=timeout)
+        p = _bench_process(args + ['--full', '--detail', detail], timeout=timeout)
         assert p.returncode == 0, p.stderr[-3000:]
         full = json.load(open(detail))
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
@@ -67,6 +67,28 @@ def test_bench_node_sharded_one_rank():
                     '--no-cpu-baseline'])
     assert d['n_gpus'] == 1 and d['parity_sample']['ok'] and d['parity_sample']['worst_rel'] < 1e-4
     assert d['exchange']['gathers_per_step'] == 1 and d['exchange']['ms_per_gather'] is not None
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_times_the_headline_only(tmp_path):
+    """`python bench.py` without --full: the headline is timed and its outputs are dumped, and nothing else runs -- no oracle check,
+    no per-stage pass, no CPU baseline, no other configuration; the ONE line still carries the contract's keys."""
+    import json
+    import numpy as np
+    p = _bench_process(['--gpus', '1', '--rooms', '6', '--length', '40000', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path / 'out'), '--detail', str(tmp_path / 'detail.json')])
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['unit'] == 'node-frames/s' and line['higher_is_better'] is True and line['dtype'] == 'f32' and line['n_gpus'] == 1
+    c = line['config']
+    assert abs(line['value'] * line['ms_per_step'] * 1e-3 / (c['rooms_per_gpu'] * c['nodes'] * c['frames']) - 1) < 1e-3
+    assert line['roofline'] is None and line['cpu_baseline'] is None and 'parity_sample' not in line
+    full = json.load(open(tmp_path / 'detail.json'))
+    assert full['stages'] is None and full['parity_sample'] is None and 'configs' not in full
+    enh = np.load(tmp_path / 'out' / 'enhanced.npy')
+    assert enh.shape == (6, 4, 40000) and np.isfinite(enh).all()
 
 
 @pytest.mark.timeout(900)

@@ -1,5 +1,5 @@
 """A bench result's parity_sample -> {rooms, worst, median, histogram, the five worst rooms} (+ per_room), for sweeps with a large --parity-rooms.
-Usage: python tools/gpu/parity_hist.py bench_detail.json out.json      (the full result `bench.py --detail` writes)"""
+Usage: python tools/gpu/parity_hist.py bench_detail.json out.json      (the full result `bench.py --full --detail` writes)"""
 import json
 import sys
 d = json.load(open(sys.argv[1]))
