@@ -387,7 +387,14 @@ int disco_mask_ivad(disco_ctx* ctx, const float* s_ref, int64_t n_sig, float* ma
  *     w_t   = intern_filter(Rss_t, Rnn_t, mu, 'gevd', rank=1)  when t % update_every == 0, else w_{t-1}
  *     out_t = w_t^H v_t ,   v_t = [X_k(t,f,:) ; Z_j(t,f) j<k ; Z_j(t,f) j>k]   (concatenate_signals, tango.py:142-155)
  * X [R][Kl][T][F][M]; Z [R][K][T][F] (all nodes; needed iff P = M + K - 1, ignored iff P = M); mask [R][Kl][T][F];
- * out [R][Kl][T][F]; w_last [R][Kl][F][P] or NULL (the filter in force at the last frame).  P <= 16. */
+ * out [R][Kl][T][F]; w_last [R][Kl][F][P] or NULL (the filter in force at the last frame).
+ * Routes by pencil size (csrc/api_online.hip; every one is launched by tests/test_gpu_online_sizes.py):
+ *     P <= 4         one thread per (room, node, bin): k_online_mwf_thread<P>
+ *     5 <= P <= 7    one thread per problem unless option "solve_thread" = 0, then the lane-group kernel
+ *     8 <= P <= 16   a group of 8 (P = 8; also 5..7 on this route) or 16 lanes per problem: k_online_mwf<P>
+ *     P > 16         DISCO_E_UNSUPPORTED
+ * Option "online_sq32" applies to the thread route only.  P other than mics or mics + nodes - 1, P > mics without Z, lambda_cor
+ * outside [0, 1), update_every < 1 or init_diag <= 0: DISCO_E_ARG, nothing written. */
 int disco_online_mwf(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, const float* mask, int P,
                      float lambda_cor, float mu, int update_every, float init_diag,
                      disco_c32* out, disco_c32* w_last, disco_stream s);

@@ -338,17 +338,20 @@ def check_online_mwf(make_engine, R=2, K=3, M=2, L=6000, n_fft=512, update_every
     return errs
 
 
-def check_online_stream(make_engine, R=2, K=3, M=2, L=6144, n_fft=512, update_every=3, chunks=(2, 5, 1, 7, 3)):
+def check_online_stream(make_engine, R=2, K=3, M=2, L=6144, n_fft=512, update_every=3, chunks=(2, 5, 1, 7, 3), options=None):
     """disco_tango_online_stream (state in, state out: the online path fed chunk by chunk) against disco_tango_online on the whole clip:
     the same output samples BIT FOR BIT, whatever the chunking -- ragged chunk sizes (cycled from `chunks`, in hops), a one-hop chunk,
     filter updates that fall inside chunks, the final frame delivered with the last chunk (last=True needs new samples: the stream is not
     flushed empty-handed) -- and the state block really carries everything
-    (a second stream interleaved on the same context does not disturb the first; a copy of the block resumes a stream)."""
+    (a second stream interleaved on the same context does not disturb the first; a copy of the block resumes a stream).
+    options: {key: value} applied with set_option before the first call (solve_thread = 0: the group kernel at P <= 7)."""
     from disco_amd import synth
     y, s, n = synth.make_rooms_numpy(R, K=K, M=M, L=L)
     H = n_fft // 2
     assert L % H == 0
     eng = make_engine(rooms=R, nodes=K, mics=M, length=L, n_fft=n_fft)
+    for key, value in (options or {}).items():
+        eng.set_option(key, value)
     T, F = eng.T, eng.F
     mask = eng.mask_oracle(s[:, :, 0].reshape(R * K, L), n[:, :, 0].reshape(R * K, L)).reshape(R, K, T, F).numpy()
     whole = eng.tango_online(y, mask, update_every=update_every, want_z=False, want_yf=False)[0].numpy()

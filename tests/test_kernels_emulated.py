@@ -73,7 +73,8 @@ def test_emu_online_golden(make_engine, golden_dir):
 
 
 def test_emu_online_stream(make_engine):
-    """The streaming form of the online path == the whole-clip call, bit for bit, for several chunkings (group and thread kernels)."""
+    """The streaming form of the online path == the whole-clip call, bit for bit, for several chunkings.  With the default options both
+    shapes (P <= 7) run the thread kernel; the group kernel's streams are in tests/test_online_sizes_emulated.py."""
     print(pc.check_online_stream(make_engine, R=1, K=2, M=2, L=3072, update_every=3))
     print(pc.check_online_stream(make_engine, R=1, K=4, M=4, L=2048, update_every=2, chunks=(3, 1, 2)))
 
