@@ -47,6 +47,7 @@ PROTOTYPES = {
     'disco_owned_bytes': (_sz, [_vp]),
     'disco_set_node_shard': (_int, [_vp, _int, _int]),
     'disco_set_z_blocks': (_int, [_vp, _int]),
+    'disco_set_lengths': (_int, [_vp, _vp, _int]),
     'disco_set_tuning': (_int, [_vp, _int, _int, _int, _int]),
     'disco_set_option': (_int, [_vp, C.c_char_p, _int]),
     'disco_get_option': (_int, [_vp, C.c_char_p, C.POINTER(_int)]),

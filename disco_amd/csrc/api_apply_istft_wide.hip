@@ -64,6 +64,7 @@ int apply_istft_wide(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, con
     a.Kl = ctx->Kl;
     a.k0 = ctx->k0;
     a.zblk = ctx->zblk;
+    a.lens = ctx->d_lens;
     bool launched = false;
 #define X_(M_, K_)                                                                                                                          \
     if (!launched && c.mics == M_ && K == K_) {                                                                                             \

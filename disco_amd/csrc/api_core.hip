@@ -82,6 +82,7 @@ extern "C" int disco_create(disco_ctx** out, const disco_cfg* cfg) {
     ctx->d_tw_conv = nullptr;
     ctx->conv_ws = nullptr;
     ctx->conv_ws_bytes = 0;
+    ctx->d_lens = ctx->d_lens_own = nullptr;
     ctx->err[0] = 0;
     const int N = cfg->n_fft;
     std::vector<float> win(N);
@@ -168,6 +169,10 @@ int ensure_halves(disco_ctx* ctx) {
         ch->opt[DISCO_OPT_OVERLAP_SOLVES] = 0;
         ch->stage_on = ctx->stage_on;
         ctx->half[h] = ch;
+        if (has_lengths(ctx)) {                            // its slice of the lengths (the device block stays the parent's)
+            ch->h_lens.assign(ctx->h_lens.begin() + (h ? ra : 0), ctx->h_lens.begin() + (h ? ra + rb : ra));
+            ch->d_lens = ctx->d_lens + (h ? ra : 0);
+        }
         if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) {
             const int rs = reserve_scratch(ch);
             if (rs) return drop(rs, ch->err);
@@ -197,6 +202,7 @@ extern "C" void disco_destroy(disco_ctx* ctx) {
     if (ctx->scratch2) (void)hipFree(ctx->scratch2);
     if (ctx->d_tw_conv && ctx->d_tw_conv != ctx->d_tw) (void)hipFree(ctx->d_tw_conv);
     if (ctx->conv_ws) (void)hipFree(ctx->conv_ws);
+    if (ctx->d_lens_own) (void)hipFree(ctx->d_lens_own);
     delete ctx;
 }
 
@@ -204,9 +210,62 @@ extern "C" int disco_set_node_shard(disco_ctx* ctx, int first_node, int node_cou
     DISCO_ENTER(ctx);
     if (first_node < 0 || node_count < 1 || first_node + node_count > ctx->cfg.nodes)
         return fail(ctx, DISCO_E_ARG, "disco_set_node_shard: shard outside [0, nodes)");
+    if (has_lengths(ctx) && node_count != ctx->cfg.nodes)
+        return fail(ctx, DISCO_E_UNSUPPORTED, "disco_set_node_shard: per-room lengths are set (disco_set_lengths); a node shard does not take them");
     ctx->k0 = first_node;
     ctx->Kl = node_count;
     ctx->pending_chunks = 0;
+    return 0;
+}
+
+// Per-room clip lengths.  The device block is allocated by the first call and rewritten in place by every later one (a synchronous copy:
+// this is not a compute call), so kernels -- and a hipGraph captured with lengths set -- read the present lengths from the same address.
+extern "C" int disco_set_lengths(disco_ctx* ctx, const int32_t* lengths, int n_rooms) {
+    DISCO_ENTER(ctx);
+    const disco_cfg& c = ctx->cfg;
+    if (ctx->parent) return fail(ctx, DISCO_E_ARG, "disco_set_lengths: a half-batch child follows its parent");
+    auto drop_state = [](disco_ctx* x) {                   // partial sums / reference state of other lengths must not be re-used
+        x->pending_chunks = 0;
+        x->pending_skiploc = 0;
+        x->loc_M = 0;
+        x->ref_ws = nullptr;
+    };
+    if (!lengths) {
+        ctx->h_lens.clear();
+        ctx->d_lens = nullptr;
+        drop_state(ctx);
+        for (int h = 0; h < 2; ++h)
+            if (ctx->half[h]) {
+                ctx->half[h]->h_lens.clear();
+                ctx->half[h]->d_lens = nullptr;
+                drop_state(ctx->half[h]);
+            }
+        return 0;
+    }
+    if (n_rooms != c.rooms) return fail(ctx, DISCO_E_ARG, "disco_set_lengths: n_rooms must equal cfg.rooms");
+    if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_set_lengths: per-room lengths are not supported under a node shard");
+    const int lo = c.pad_mode == DISCO_PAD_REFLECT ? c.n_fft / 2 + 1 : 1;
+    for (int r = 0; r < n_rooms; ++r)
+        if (lengths[r] < lo || lengths[r] > c.length) {
+            char m[200];
+            snprintf(m, sizeof(m), "disco_set_lengths: lengths[%d] = %d outside [%d, cfg.length = %d]%s", r, (int)lengths[r], lo, c.length,
+                     c.pad_mode == DISCO_PAD_REFLECT ? " (reflect padding needs more than n_fft/2 samples)" : "");
+            return fail(ctx, DISCO_E_ARG, m);
+        }
+    if (!ctx->d_lens_own) HIPCHK(ctx, hipMalloc((void**)&ctx->d_lens_own, (size_t)c.rooms * sizeof(int)));
+    HIPCHK(ctx, hipMemcpy(ctx->d_lens_own, lengths, (size_t)c.rooms * sizeof(int), hipMemcpyHostToDevice));
+    ctx->h_lens.assign(lengths, lengths + n_rooms);
+    ctx->d_lens = ctx->d_lens_own;
+    drop_state(ctx);
+    int r0 = 0;
+    for (int h = 0; h < 2; ++h)
+        if (ctx->half[h]) {
+            const int rh = ctx->half[h]->cfg.rooms;
+            ctx->half[h]->h_lens.assign(lengths + r0, lengths + r0 + rh);
+            ctx->half[h]->d_lens = ctx->d_lens_own + r0;
+            drop_state(ctx->half[h]);
+            r0 += rh;
+        }
     return 0;
 }
 

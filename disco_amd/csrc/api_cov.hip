@@ -72,7 +72,7 @@ int cov_finalize(disco_ctx* ctx, int chunks, int P, disco_c32* Rss, disco_c32* R
     const long long n_gf = (long long)ctx->cfg.rooms * ctx->Kl * ctx->F;
     hipLaunchKernelGGL(k_cov_finalize, dim3((unsigned)std::min<long long>((n_gf + 127) / 128, 65535)), dim3(128), 0,
                        (hipStream_t)s, (const float4*)ctx->scratch, (c32*)Rss, (c32*)Rnn, n_gf, ctx->F, chunks, P,
-                       1.0f / (float)ctx->T);
+                       1.0f / (float)ctx->T, ctx->d_lens, ctx->Kl);
     return check_launch(ctx, "k_cov_finalize");
 }
 // 17 <= P <= 32 (k_cov_wide.h): always the full triangle into `scratch` (the step-1 sums are not re-used: no skiploc)

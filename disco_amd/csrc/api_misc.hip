@@ -152,6 +152,7 @@ extern "C" int disco_band_stats(disco_ctx* ctx, const float* x, int64_t n_sig, i
 
 extern "C" int disco_mask_ivad(disco_ctx* ctx, const float* s_ref, int64_t n_sig, float* mask, disco_stream s) {
     DISCO_ENTER(ctx);
+    DISCO_REFUSE_LENGTHS(ctx, "disco_mask_ivad");
     if (!s_ref || !mask || n_sig < 1) return fail(ctx, DISCO_E_ARG, "disco_mask_ivad: bad argument");
     const disco_cfg& c = ctx->cfg;
     if ((c.length + c.hop - 1) / c.hop > VAD_MAX_SEG) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_mask_ivad: signal longer than 4096 hops");

@@ -89,6 +89,7 @@ extern "C" int disco_online_mwf(disco_ctx* ctx, const disco_c32* X, const disco_
                                 float lambda_cor, float mu, int update_every, float init_diag, disco_c32* out,
                                 disco_c32* w_last, disco_stream s) {
     DISCO_ENTER(ctx);
+    DISCO_REFUSE_LENGTHS(ctx, "disco_online_mwf");
     const OnlineWalk wk{ctx->T, ctx->T, 0, ctx->T, nullptr, 0, 0};
     return online_mwf_walk(ctx, X, Z, mask, P, lambda_cor, mu, update_every, init_diag, out, w_last, wk, s);
 }
@@ -97,6 +98,7 @@ extern "C" int disco_tango_online(disco_ctx* ctx, const float* y, const float* m
                                   int update_every, float init_diag, float* out, disco_c32* z_y, disco_c32* yf,
                                   void* workspace, size_t workspace_bytes, disco_stream s) {
     DISCO_ENTER(ctx);
+    DISCO_REFUSE_LENGTHS(ctx, "disco_tango_online");
     if (!y || !mask_z || !mask_w || !out) return fail(ctx, DISCO_E_ARG, "disco_tango_online: null argument");
     if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_tango_online: node shard active, drive disco_online_mwf around an all-gather of z");
     const disco_cfg& c = ctx->cfg;
@@ -177,6 +179,7 @@ extern "C" int disco_tango_online_stream(disco_ctx* ctx, const float* y_new, int
                                          float lambda_cor, int update_every, float init_diag, int64_t hops_before, int last, void* state,
                                          float* out, void* workspace, size_t workspace_bytes, disco_stream s) {
     DISCO_ENTER(ctx);
+    DISCO_REFUSE_LENGTHS(ctx, "disco_tango_online_stream");
     const disco_cfg& c = ctx->cfg;
     if (!y_new || !mask_z || !mask_w || !out || !state || !workspace) return fail(ctx, DISCO_E_ARG, "disco_tango_online_stream: null argument");
     if (n_hops < 1 || hops_before < 0 || update_every < 1)

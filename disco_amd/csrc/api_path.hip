@@ -193,10 +193,14 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
         return;
     }
     // step 1 (tango.py:326-376): STFT + covariance in one pass, solve straight from the partial sums
-    st.push_back({nullptr, false, [=](disco_stream s) { int ch = 1; return stft_cov_partials(ctx, y, mask_z, X, &ch, s); }});
+    const bool fused_route = c.nodes > 1 && P2 <= 8 && !(c.flags & DISCO_FLAG_STAGED_STEP2);
+    // per-room lengths: both readers of X on the fused route without yf (k_step2_cov_fused, k_step2_apply_istft) stop at a room's own
+    // frames, so the frames of X beyond them need not be written; every other route reads them and finds the zeros it relies on
+    const bool x_zeros = !(fused_route && !yf && c.n_fft == 512 && step2_apply_istft_ok(ctx));
+    st.push_back({nullptr, false, [=](disco_stream s) { int ch = 1; return stft_cov_partials(ctx, y, mask_z, X, &ch, s, true, x_zeros); }});
     st.push_back({"solve1", true, solve_pending(w)});
 
-    if (c.nodes > 1 && P2 <= 8 && !(c.flags & DISCO_FLAG_STAGED_STEP2)) {
+    if (fused_route) {
         // step 2 on the on-chip z exchange (default whenever all nodes of a room share the GPU and P <= 8)
         // same mask array in both steps (oracle masks; a DNN mask re-used, tango.py:388-389): the leading M x M block of the
         // step-2 covariances IS the step-1 covariance still held as partial sums -> not recomputed
@@ -393,7 +397,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
             HIPCHK(ctx, hipMemcpyAsync(mz, mask_z_in, mask_b, hipMemcpyDeviceToDevice, st));
         } else {
             hipLaunchKernelGGL(k_tf_mask_channel, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)Xs, (const c32*)Xn, mz, nTF, M, c.ref_mic,
-                               c.mask_type, c.mask_pow, thr);
+                               c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
             if ((rc = check_launch(ctx, "k_tf_mask_channel"))) return rc;
         }
         // ---- step 1: local statistics, filter, compressed signals (tango.py:343-376)
@@ -428,7 +432,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
         HIPCHK(ctx, hipMemcpyAsync(mw, mask_w_in, mask_b, hipMemcpyDeviceToDevice, st));
     } else {
         hipLaunchKernelGGL(k_tf_mask_channel, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)Xs, (const c32*)Xn, mw, nTF, M, 0,
-                           c.mask_type, c.mask_pow, thr);
+                           c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
         if ((rc = check_launch(ctx, "k_tf_mask_channel"))) return rc;
     }
     if ((rc = give(out->mask_w, mw, mask_b))) return rc;
@@ -446,7 +450,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
                 break;
             case DISCO_MZ_COMPRESSED: {           // the sender's mask from ITS compressed target / noise (get_mask(z_s, z_n), tango.py:402-403)
                 hipLaunchKernelGGL(k_tf_mask, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)zs, (const c32*)zn_, mc, nTF, c.mask_type,
-                                   c.mask_pow, thr);
+                                   c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
                 hipLaunchKernelGGL(k_mask_rows, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)zy, (const float*)mc, (c32*)rows_s, (c32*)rows_n, nTF);
                 Zs_rows = rows_s;
                 Zn_rows = rows_n;

@@ -26,6 +26,7 @@ extern "C" int disco_step2_apply_fused(disco_ctx* ctx, const disco_c32* X, const
     a.F = ctx->F;
     const int tiles = (ctx->F - 1) / 64;
     a.chunks = step2_chunks(ctx, tiles + 1);
+    a.lens = ctx->d_lens;
     const long long nblk = (long long)c.rooms * (tiles + 1) * a.chunks;
     if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_apply_fused: batch too large");
     bool launched = false;

@@ -49,6 +49,7 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     a.T = ctx->T;
     a.F = ctx->F;
     a.chunks = chunks;
+    a.lens = ctx->d_lens;
     const long long nblk = (long long)c.rooms * (tiles + 1) * chunks;
     if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: batch too large");
     bool launched = false;

@@ -7,9 +7,9 @@ using namespace disco_host;
 
 template <int M, int K>
 static bool launch_apply_istft(const Step2Args& a, float* out, const float* win, const c32* tw, int L, int bpr, int pairs, dim3 grid,
-                               hipStream_t st) {
+                               hipStream_t st, const int* lens) {
     if constexpr (sizeof(ApplyIstftShared<512, M, K>) <= 160 * 1024) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_apply_istft<512, M, K>), grid, dim3(64 * K), 0, st, a, out, win, tw, L, bpr, pairs);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_apply_istft<512, M, K>), grid, dim3(64 * K), 0, st, a, out, win, tw, L, bpr, pairs, lens);
         return true;
     } else {
         return false;
@@ -49,6 +49,7 @@ extern "C" int disco_step2_apply_istft_fused(disco_ctx* ctx, const disco_c32* X,
     a.T = ctx->T;
     a.F = ctx->F;
     a.chunks = 1;
+    a.lens = ctx->d_lens;
     const int n_seg = (c.length + c.hop - 1) / c.hop;
     // frame pairs per workgroup: as many as possible (<= 64) while leaving >= ~8192 waves (a workgroup has K of them)
     const long long units = (long long)ctx->geom_rooms * K;
@@ -64,7 +65,7 @@ extern "C" int disco_step2_apply_istft_fused(disco_ctx* ctx, const disco_c32* X,
     if (!tried && M == M_ && K == KR_ + 1) {                                                                         \
         tried = true;                                                                                                \
         launched = launch_apply_istft<M_, KR_ + 1>(a, out, ctx->d_win, ctx->d_tw, c.length, bpr, pairs, dim3((unsigned)nblk), \
-                                                   (hipStream_t)s);                                                  \
+                                                   (hipStream_t)s, ctx->d_lens);                                     \
     }
     DISCO_FOR_MKR(X_)
 #undef X_
@@ -91,7 +92,7 @@ int stft_apply_istft(disco_ctx* ctx, const float* y, const disco_c32* w, float* 
 #define C_(M_)                                                                                                          \
     case M_:                                                                                                            \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_apply_istft<512, M_>), grid, block, 0, (hipStream_t)s, y, (const c32*)w, out, ctx->d_win, \
-                           ctx->d_tw, c.length, ctx->T, c.pad_mode, runs, pairs, items);                                \
+                           ctx->d_tw, c.length, ctx->T, c.pad_mode, runs, pairs, items, ctx->d_lens, c.nodes);          \
         break;
         C_(1) C_(2) C_(3) C_(4)
 #undef C_

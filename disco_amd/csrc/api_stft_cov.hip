@@ -10,13 +10,14 @@ using namespace disco_host;
 // ---------------------------------------------------------------------------------------------------------
 template <int N, bool STORE = true>
 static bool launch_stft_cov(int M, dim3 grid, hipStream_t st, const float* y, const float* mask, c32* X, float4* part,
-                            const float* win, const c32* tw, int L, int T, int pad_mode, int chunks, int runw) {
+                            const float* win, const c32* tw, int L, int T, int pad_mode, int chunks, int runw, const int* lens, int spr,
+                            int zero_beyond) {
     const dim3 block(64 * STFT_WAVES);
     switch (M) {
 #define C_(M_)                                                                                                          \
     case M_:                                                                                                            \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
-                           chunks, runw);                                                                               \
+                           chunks, runw, lens, spr, zero_beyond);                                                       \
         return true;
         C_(1) C_(2) C_(3) C_(4) C_(5) C_(6)
 #undef C_
@@ -26,7 +27,7 @@ static bool launch_stft_cov(int M, dim3 grid, hipStream_t st, const float* y, co
 #define C_(M_)                                                                                                          \
     case M_:                                                                                                            \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
-                           chunks, runw);                                                                               \
+                           chunks, runw, lens, spr, zero_beyond);                                                       \
         return true;
             C_(7) C_(8)
 #undef C_
@@ -56,7 +57,10 @@ int stft_cov_chunks(const disco_ctx* ctx, int* runw_out) {
 }
 
 // store = false (internal, single-node path): the spectra are not written (X may be NULL); only for shapes the fused kernel takes
-int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, int* chunks_out, disco_stream s, bool store) {
+// zero_beyond = false (internal, per-room lengths): the frames of X beyond a room's clip are left unwritten -- only for a caller whose every
+// reader of X knows the lengths (the fused route of disco_tango_enhance)
+int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, int* chunks_out, disco_stream s, bool store,
+                      bool zero_beyond) {
     if (!y || !mask_z || (store && !X)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: null argument");
     // (works on a node shard too: nothing in this pass looks beyond one node -- X, masks and partial sums then hold the shard's Kl nodes per room)
     const disco_cfg& c = ctx->cfg;
@@ -83,14 +87,14 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
     const bool ok = !store
         ? STAGE(ctx, s, "stft_cov1_nostore", c.n_fft == 512
             ? (launch_stft_cov<512, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
-                                           ctx->T, c.pad_mode, chunks, runw))
+                                           ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0))
             : (launch_stft_cov<1024, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
-                                            ctx->T, c.pad_mode, chunks, runw)))
+                                            ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)))
         : STAGE(ctx, s, "stft_cov1", c.n_fft == 512
         ? launch_stft_cov<512>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
-                               ctx->T, c.pad_mode, chunks, runw)
+                               ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)
         : launch_stft_cov<1024>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
-                                ctx->T, c.pad_mode, chunks, runw));
+                                ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0));
     if (!ok) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: unsupported mic count");
     *chunks_out = chunks;
     ctx->pending_chunks = chunks;

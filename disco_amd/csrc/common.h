@@ -152,6 +152,13 @@ __device__ __forceinline__ long long z_plane(long long r, int j, int K, long lon
     return ((long long)(j / zblk) * R + r) * zblk + (j % zblk);
 }
 
+// Per-room clip lengths (disco_set_lengths): `lens` is the context's device array of one length per room, nullptr for the uniform
+// batch.  The room index must be wave-uniform (from blockIdx, or from wave_id()), so that the length comes through the scalar path
+// and lives in an SGPR; readfirstlane states that for the value as well.  T_r = 1 + L_r / hop follows from it.
+__device__ __forceinline__ int room_length(const int* __restrict__ lens, long long room, int Lmax) {
+    return lens ? __builtin_amdgcn_readfirstlane(lens[room]) : Lmax;
+}
+
 // reflect / zero padded sample fetch, branch-free: p is the index into the un-padded signal of length L.
 // The load is unconditional (clamped index); out-of-range samples of constant padding are zeroed by a select.
 __device__ __forceinline__ float load_padded(const float* __restrict__ x, int p, int L, int pad_mode) {

@@ -76,6 +76,12 @@ struct disco_ctx {
     };
     bool stage_on;
     std::vector<StageRec> stages;
+    // per-room clip lengths (disco_set_lengths).  d_lens is what the kernels receive: NULL for the uniform batch, else cfg.rooms ints on
+    // the device -- the context's own block (d_lens_own, allocated by the first disco_set_lengths and rewritten in place by later ones),
+    // or, in a half-batch child, its slice of the parent's block.  h_lens is the host copy (empty = none).
+    std::vector<int32_t> h_lens;
+    int* d_lens;
+    int* d_lens_own;
     char err[512];
 };
 
@@ -166,6 +172,11 @@ struct StageScope {
 };
 #define STAGE(ctx, s, name, call) ([&]() { StageScope stage_scope_((ctx), (s), (name)); return (call); }())
 
+// entry points that do not take per-room lengths (the online mode, disco_mask_ivad, anything under a node shard) refuse while they are set
+static inline bool has_lengths(const disco_ctx* ctx) { return ctx->d_lens != nullptr; }
+#define DISCO_REFUSE_LENGTHS(ctx, who) \
+    if (has_lengths(ctx)) return fail((ctx), DISCO_E_UNSUPPORTED, who ": per-room lengths are set (disco_set_lengths); not supported here")
+
 // whole-path entry points work on all nodes of a room and on their own plain [R][K] exchanged-signal arrays
 static inline bool sharded(const disco_ctx* ctx) { return ctx->Kl != ctx->cfg.nodes || ctx->zblk != ctx->cfg.nodes; }
 
@@ -210,8 +221,13 @@ bool overlap_applies(const disco_ctx* ctx);
 int acquire_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, const WsLayout& l, char** ws_out, const char* who);
 
 // transforms of signals of any length with the context's window / FFT size / padding (api_stft.hip)
-int stft_any(disco_ctx* ctx, const float* x, int64_t n_sig, int chans, disco_c32* X, int L, int T, disco_stream s);
-int istft_any(disco_ctx* ctx, const disco_c32* Z, int64_t n_sig, float* out, int L, int T, disco_stream s, bool solo);
+// lens / sig_per_room: per-room clip lengths (device array, signal g belongs to room g / sig_per_room) or NULL
+int stft_any(disco_ctx* ctx, const float* x, int64_t n_sig, int chans, disco_c32* X, int L, int T, disco_stream s, const int* lens = nullptr,
+             int sig_per_room = 1);
+int istft_any(disco_ctx* ctx, const disco_c32* Z, int64_t n_sig, float* out, int L, int T, disco_stream s, bool solo, const int* lens = nullptr,
+              int sig_per_room = 1);
+// per-room lengths and the n_sig of a stage call: signal g belongs to room g / (n_sig / rooms); 0, or an error code with the message set
+int lengths_sig_per_room(disco_ctx* ctx, int64_t n_sig, const char* who, int* sig_per_room);
 
 // stages (each leaves its partial sums pending in the context; see the definitions)
 int cov_finalize(disco_ctx* ctx, int chunks, int P, disco_c32* Rss, disco_c32* Rnn, disco_stream s);
@@ -221,7 +237,7 @@ bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask);
 int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, int* chunks_out,
                       disco_stream s, bool store_z = true);
 int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, int* chunks_out, disco_stream s,
-                      bool store = true);
+                      bool store = true, bool zero_beyond = true);
 int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out, int* chunks_out,
                        disco_stream s, bool skiploc = false);
 int stft_apply_istft(disco_ctx* ctx, const float* y, const disco_c32* w, float* out, disco_stream s);

@@ -987,8 +987,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__((64 * cov_split_waves<KR, SKIPLO
 }
 
 // part [n_gf/F][chunks][F][NP] -> Rss, Rnn [n_gf][P][P], mean over T, Hermitian mirror.
+// lens (per-room clip lengths, nullptr: none): unit g belongs to room g / units_per_room, whose mean is over its own T_r = 1 + L_r / hop frames
 static __global__ void k_cov_finalize(const float4* __restrict__ part, c32* __restrict__ Rss, c32* __restrict__ Rnn,
-                               long long n_gf, int F, int chunks, int P, float inv_T) {
+                               long long n_gf, int F, int chunks, int P, float inv_T, const int* __restrict__ lens, int units_per_room) {
     const int NP = P * (P + 1) / 2;
     for (long long gf = (long long)blockIdx.x * blockDim.x + threadIdx.x; gf < n_gf; gf += (long long)gridDim.x * blockDim.x) {
         const long long g = gf / F;
@@ -1006,7 +1007,7 @@ static __global__ void k_cov_finalize(const float4* __restrict__ part, c32* __re
                     sz += (double)p.z;
                     sw += (double)p.w;
                 }
-                const double it = (double)inv_T;
+                const double it = lens ? (double)(1.0f / (float)(1 + lens[g / units_per_room] / (F - 1))) : (double)inv_T;
                 float4 s = make_float4((float)(sx * it), (float)(sy * it), (float)(sz * it), (float)(sw * it));
                 if (i == j) s.y = s.w = 0.f;
                 c32* rs = Rss + gf * P * P;

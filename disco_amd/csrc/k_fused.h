@@ -24,6 +24,7 @@ struct Step2Args {
     c32* yf;             // [R][K][T][F]         (apply kernel)
     float4* part;        // [R*K][chunks][F][NP] (cov kernel)
     int K, T, F, chunks;
+    const int* lens;     // per-room clip lengths (disco_set_lengths) or NULL
 };
 
 // (room, bin tile | Nyquist, frame chunk) of a block and the (bin, first frame, frame stride) of a lane
@@ -88,14 +89,23 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K) void k_step2_cov_fused(S
     c32 acc_s[NP], acc_n[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) acc_s[q] = acc_n[q] = make_float2(0.f, 0.f);
+    // per-room lengths: the frames of this chunk beyond the room's T_r hold zeros in X -- they would add nothing, so the chunk ends at
+    // T_r (workgroup-uniform) and their z is written as the zeros it is
+    int t1 = gm.t1;
+    if (a.lens) {
+        const int Tr = 1 + room_length(a.lens, gm.r, 0) / (F - 1);
+        if (zg)
+            for (int t = max(gm.t0, Tr) + gm.t_lane; t < gm.t1; t += gm.t_stride) zg[(long long)t * F + f] = make_float2(0.f, 0.f);
+        t1 = min(t1, Tr);
+    }
     // software pipeline: the next U frames are requested before the current ones are reduced, so every wave
     // keeps 2*U*(8M+4) bytes per lane in flight while it computes
     auto fetch = [&](int tu, c32 (*xx)[M], float* mm) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = tu + u * gm.t_stride + gm.t_lane;
-            const bool live = t < gm.t1;
-            const long long tf = (long long)(live ? t : gm.t1 - 1) * F + f;      // always a valid frame: loads stay unconditional
+            const bool live = t < t1;
+            const long long tf = (long long)(live ? t : t1 - 1) * F + f;      // always a valid frame: loads stay unconditional
 #pragma unroll
             for (int i = 0; i < M; ++i) xx[u][i] = Xg[tf * M + i];      // raw: consumed (and zeroed if !live) after the barrier
             mm[u] = mg[tf];
@@ -105,19 +115,19 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K) void k_step2_cov_fused(S
     float m[U], mn[U];
     fetch(gm.t0, x, m);
     int buf = 0;
-    for (int tu = gm.t0; tu < gm.t1; tu += U * gm.t_stride, buf ^= 1) {
+    for (int tu = gm.t0; tu < t1; tu += U * gm.t_stride, buf ^= 1) {
         fetch(tu + U * gm.t_stride, xn, mn);           // frames >= t1 come back as zeros (predicated off)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = tu + u * gm.t_stride + gm.t_lane;
             const c32 z = filt_conj<M>(wl, x[u]);
             zbuf[buf][u][k][lane] = z;
-            if (t < gm.t1 && zg) zg[(long long)t * F + f] = z;
+            if (t < t1 && zg) zg[(long long)t * F + f] = z;
         }
         __syncthreads();             // one barrier per U frames; zbuf is double buffered, so none is needed after the reads
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const bool live = tu + u * gm.t_stride + gm.t_lane < gm.t1;       // frames past the chunk were loaded clamped: weigh them 0
+            const bool live = tu + u * gm.t_stride + gm.t_lane < t1;       // frames past the chunk were loaded clamped: weigh them 0
             const float ms = live ? m[u] : 0.f, mc = live ? 1.f - m[u] : 0.f;
             c32 uu[P];
 #pragma unroll
@@ -269,14 +279,16 @@ __device__ __forceinline__ float ola_last_segment_factor(const float* __restrict
 }
 // emits hop segments tA - 1 (carry + lower half of A; skipped for a run's first pair, it belongs to the predecessor) and tA
 // (upper half of A + lower half of B); carry <- upper half of B
+// T, L: the signal's own frame count and length (per-room lengths: T_r, L_r); Tw, Lw: those of the array (Tmax, Lmax) -- segments and
+// samples between the two are written as exact zeros.  Without lengths the two pairs are equal.
 template <int N>
 __device__ __forceinline__ void ola_emit_pair(const c32* v, float* carry, const OlaWeights<N>& ow, float* __restrict__ og,
-                                              const float* __restrict__ win, int tA, bool first_pair, int T, int L, int lane) {
+                                              const float* __restrict__ win, int tA, bool first_pair, int T, int L, int Tw, int Lw, int lane) {
     constexpr int EH = FftPlan<N>::E / 2, H = N / 2;
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
         const int seg = tA - 1 + which;
-        const bool emit = (which == 1 || !first_pair) && seg >= 0 && seg < T;       // wave-uniform
+        const bool emit = (which == 1 || !first_pair) && seg >= 0 && seg < Tw;      // wave-uniform
         float val[EH];
 #pragma unroll
         for (int e = 0; e < EH; ++e)
@@ -292,13 +304,23 @@ __device__ __forceinline__ void ola_emit_pair(const c32* v, float* carry, const 
                 for (int e = 0; e < EH; ++e) store_stream4(&o[64 * e], val[e]);
             } else {
 #pragma unroll
-                for (int e = 0; e < EH; ++e)
-                    if ((long long)seg * H + lane + 64 * e < L) store_stream4(&o[64 * e], val[e]);
+                for (int e = 0; e < EH; ++e) {
+                    const long long pos = (long long)seg * H + lane + 64 * e;
+                    if (pos < Lw) store_stream4(&o[64 * e], pos < L ? val[e] : 0.f);
+                }
             }
         }
     }
 #pragma unroll
     for (int e = 0; e < EH; ++e) carry[e] = -v[e + EH].y * ow.cB[e];
+}
+
+// per-room lengths: a wave whose hop segments [s0, s0 + n_seg) all lie beyond its room's clip writes their zeros and is done
+template <int N>
+__device__ __forceinline__ void ola_zero_segments(float* __restrict__ og, int s0, int n_seg, int Lw, int lane) {
+    constexpr int H = N / 2;
+    const long long p0 = (long long)s0 * H, p1 = min((long long)(s0 + n_seg) * H, (long long)Lw);
+    for (long long pos = p0 + lane; pos < p1; pos += 64) og[pos] = 0.f;
 }
 
 #ifndef DISCO_AI_PREFETCH
@@ -316,7 +338,7 @@ struct alignas(16) ApplyIstftShared {
 template <int N, int M, int K>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 : 1) void k_step2_apply_istft(Step2Args a, float* __restrict__ out,
                                                                const float* __restrict__ win, const c32* __restrict__ tw,
-                                                               int L, int blocks_per_room, int pairs) {
+                                                               int L, int blocks_per_room, int pairs, const int* __restrict__ lens) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, H = N / 2, EH = E / 2, NJ = EH + 1, P = M + K - 1;
     __shared__ ApplyIstftShared<N, M, K> sh;
     const int k = wave_id(), lane = threadIdx.x & 63;
@@ -324,6 +346,13 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
     const int s0 = (int)(blockIdx.x % blocks_per_room) * (2 * pairs - 1);       // first hop segment == first frame
     const int T = a.T;
     const long long g = r * K + k;
+    // L, T: the pitch of the arrays; Lr, Tr: the room's own clip (disco_set_lengths; the same without lengths).  X holds zeros in the
+    // frames beyond Tr, so only the overlap-add has to know: the window sum of the last segment and where the zeros begin.
+    const int Lr = room_length(lens, r, L), Tr = lens ? 1 + Lr / H : T;
+    if (lens && s0 >= Tr) {                        // (workgroup-uniform, before the first barrier) a run wholly in the padding
+        ola_zero_segments<N>(out + g * (long long)L, s0, 2 * pairs - 1, L, lane);
+        return;
+    }
     const c32* Xg = a.X + (g * T * (long long)F) * M;
     // the room's local filters -> LDS (every wave needs all of them only through z; its own row is read per frame)
     if constexpr (K > 1) {
@@ -413,10 +442,10 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
                 }
             }
         }
-        if (tA + 1 >= T) {                           // wave-uniform, last pair of a signal only: frames past the end contribute nothing
+        if (tA + 1 >= Tr) {                          // wave-uniform, last pair of a signal only: frames past the end contribute nothing
 #pragma unroll
             for (int fr = 0; fr < 2; ++fr)
-                if (tA + fr >= T) {
+                if (tA + fr >= Tr) {
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) yf[fr][j] = make_float2(0.f, 0.f);
                 }
@@ -439,7 +468,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
                     }
         }
         // ---- window, overlap-add: segment (tA-1) = carry + A[lo], segment tA = A[hi] + B[lo], carry <- B[hi]
-        ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, T, L, lane);
+        ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, Tr, Lr, T, L, lane);
         // zbuf is rewritten by the next pair only after every wave has passed the next __syncthreads... but a fast wave
         // could reach its z stores of pair pr+1 while a slow one still reads zbuf of pair pr: fence the reuse
         if constexpr (K > 1) __syncthreads();
@@ -475,6 +504,7 @@ struct ApplyIstftWideArgs {
     c32* yf;             // [R][K][T][F] or NULL (only when the caller wants the filtered spectra)
     int T, L, pairs, chunks;
     long long R;
+    const int* lens;     // per-room clip lengths (disco_set_lengths) or NULL
     // a node shard (disco_set_node_shard / disco_set_z_blocks): X, w, out, yf hold the Kl nodes [k0, k0 + Kl) of every room, Z the z of ALL K
     // nodes in planes [K / zblk][R][zblk] (z_plane, common.h); the whole room: Kl = K, k0 = 0, zblk = K
     int Kl, k0, zblk;
@@ -518,6 +548,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
     const int run_len = 2 * a.pairs - 1;
     const int s_base = chunk * NR * run_len;                                 // run u starts at frame (= hop segment) s_base + u * run_len
     const long long TF = (long long)T * F;
+    // the room's own clip (disco_set_lengths; T, a.L without lengths): X and Z hold zeros in the frames beyond Tr, so what has to know is
+    // the overlap-add (window sum of the last segment, where the zeros begin) and the spectra handed out
+    const int Lr = room_length(a.lens, r, a.L), Tr = a.lens ? 1 + Lr / (N / 2) : T;
     auto frame_of = [&](int pr, int u, int fr) { return s_base + u * run_len + 2 * pr + fr; };
     // tables every wave reads: the Nyquist bin's taps (conjugated once), the transform waves' twiddles and overlap-add weights
     if (threadIdx.x < P) {
@@ -645,8 +678,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
                         ai = x[M - 1].y + z[KR - 1].y;
                     }
                     const int t = frame_of(pr, u, fr);
-                    ring[2 * u + fr][f] = t < T ? make_float2(ar, ai) : make_float2(0.f, 0.f);
-                    if (yg && t < T) yg[(long long)t * F + f] = make_float2(ar, ai);
+                    const c32 yv = t < Tr ? make_float2(ar, ai) : make_float2(0.f, 0.f);
+                    ring[2 * u + fr][f] = yv;
+                    if (yg && t < T) yg[(long long)t * F + f] = yv;
                 }
             }
             if (n_ld) sh.nyq[wv][lane] = make_float4(nv[0], nv[1], nv[2], nv[3]);
@@ -670,8 +704,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
                     ar = fmaf(w_.x, v.x, fmaf(-w_.y, v.y, ar));
                     ai = fmaf(w_.x, v.y, fmaf(w_.y, v.x, ai));
                 }
-                ring[wv][F - 1] = tn < T ? make_float2(ar, ai) : make_float2(0.f, 0.f);
-                if (yg && tn < T) yg[(long long)tn * F + (F - 1)] = make_float2(ar, ai);
+                const c32 yv = tn < Tr ? make_float2(ar, ai) : make_float2(0.f, 0.f);
+                ring[wv][F - 1] = yv;
+                if (yg && tn < T) yg[(long long)tn * F + (F - 1)] = yv;
             }
             __syncthreads();                            // ring pr & 1 is complete; the transform waves have read ring (pr - 1) & 1
         }
@@ -722,7 +757,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
                     ow.cA[e] = sh.olw[e][lane];
                     ow.cB[e] = sh.olw[EH + e][lane];
                 }
-                ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, T, a.L, lane);
+                ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, Tr, Lr, T, a.L, lane);
             }
         }
     }
@@ -756,7 +791,8 @@ template <int N, int M>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO_SAI_TAPS_LDS ? 3 : 2) : 1) void k_stft_apply_istft(const float* __restrict__ x, const c32* __restrict__ wf,
                                                                                     float* __restrict__ out, const float* __restrict__ win,
                                                                                     const c32* __restrict__ tw, int L, int T, int pad_mode,
-                                                                                    int runs_per_node, int pairs, long long n_witems) {
+                                                                                    int runs_per_node, int pairs, long long n_witems,
+                                                                                    const int* __restrict__ lens, int sig_per_room) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, H = N / 2, EH = E / 2, NJ = EH + 1, CHP = (M + 1) / 2;
     constexpr bool TL = DISCO_SAI_TAPS_LDS != 0;
     __shared__ StftApplyShared<N, CHP> sh;
@@ -765,6 +801,12 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
     if (item >= n_witems) return;                  // no block-level synchronisation anywhere below
     const long long g = item / runs_per_node;
     const int s0 = (int)(item % runs_per_node) * (2 * pairs - 1);             // first hop segment == first frame
+    // L, T: the pitch of the arrays; Lr, Tr: the room's own clip (disco_set_lengths; the same without lengths)
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / H : T;
+    if (lens && s0 >= Tr) {                        // a run wholly in the padding: zeros, no sample touched (no barrier in this kernel)
+        ola_zero_segments<N>(out + g * (long long)L, s0, 2 * pairs - 1, L, lane);
+        return;
+    }
     c32* buf = sh.buf[wave];
     WaveTw<N> wtw;
     wtw.init(tw, lane);
@@ -802,7 +844,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
     }
     c32 raw[CHP][E];
 #pragma unroll
-    for (int p = 0; p < CHP; ++p) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], min(s0, T - 1), L, pad_mode, lane);
+    for (int p = 0; p < CHP; ++p) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], min(s0, Tr - 1), Lr, pad_mode, lane);
     OlaWeights<N> ow;
     ow.init(win, lane);
     float carry[EH];
@@ -822,7 +864,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
 #pragma unroll
                     for (int e = 0; e < EH; ++e) nxt[p][e] = make_float2(0.25f * e + lane, 1.f);
                 } else {
-                    load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], min(t + 1, T - 1), L, pad_mode, lane);
+                    load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], min(t + 1, Tr - 1), Lr, pad_mode, lane);
                 }
             }
 #pragma unroll
@@ -848,7 +890,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
                     yf[fr][j] = acc;
                 });
             }
-            if (t >= T) {                            // frames past the signal contribute nothing
+            if (t >= Tr) {                           // frames past the signal contribute nothing
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) yf[fr][j] = make_float2(0.f, 0.f);
             }
@@ -867,7 +909,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
         irfft_pair_pack<N>(yf[0], yf[1], v, lane);       // cross-lane, no LDS round trip (fft.h)
         if (!(DISCO_SAI_EXP & 2)) fft_wave<N>(v, wtw, buf, lane);
         // ---- window, overlap-add: segment (tA-1) = carry + A[lo], segment tA = A[hi] + B[lo], carry <- B[hi]
-        if (!(DISCO_SAI_EXP & 4)) ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, T, L, lane);
+        if (!(DISCO_SAI_EXP & 4)) ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, Tr, Lr, T, L, lane);
         else if (v[0].x == 123456.f) og[lane] = v[1].y;     // (keeps the arithmetic alive)
     }
 }

@@ -94,7 +94,7 @@ template <int N, int CHP>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_stft(const float* __restrict__ x, c32* __restrict__ X,
                                                            const float* __restrict__ win, const c32* __restrict__ tw,
                                                            int chans, int L, int T, int pad_mode, int runs_per_sig,
-                                                           long long n_witems) {
+                                                           long long n_witems, const int* __restrict__ lens, int sig_per_room) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, NJ = E / 2 + 1, EH = E / 2;
     __shared__ StftShared<N> sh;
     const int wave = wave_id(), lane = threadIdx.x & 63;
@@ -102,7 +102,16 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_stft(con
     if (item >= n_witems) return;                  // no block-level synchronisation anywhere below
     const long long g = item / runs_per_sig;
     const int t0 = (int)(item % runs_per_sig) * STFT_RUN;
-    const int t1 = min(T, t0 + STFT_RUN);
+    // L, T: the pitch of the arrays; Lr, Tr: the room's own clip (disco_set_lengths; the same without lengths)
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / (N / 2) : T;
+    if (lens) {                                    // frames at or beyond T_r do not exist: exact zeros, no sample touched
+        for (int t = max(t0, Tr); t < min(T, t0 + STFT_RUN); ++t) {
+            c32* Xo = X + ((g * T + t) * (long long)F) * chans;
+            for (int i = lane; i < F * chans; i += 64) Xo[i] = make_float2(0.f, 0.f);
+        }
+        if (t0 >= Tr) return;
+    }
+    const int t1 = min(Tr, t0 + STFT_RUN);
     WaveTw<N> wtw;
     wtw.init(tw, lane);
     float w[E];
@@ -116,13 +125,13 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_stft(con
     }
     c32 raw[CHP][E];
 #pragma unroll
-    for (int p = 0; p < CHP; ++p) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], t0, L, pad_mode, lane);
+    for (int p = 0; p < CHP; ++p) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], t0, Lr, pad_mode, lane);
     for (int t = t0; t < t1; ++t) {
         c32 nxt[CHP][EH];
         {
-            const int tn = min(t + 1, T - 1);              // clamped: harmless reload at the end of a run
+            const int tn = min(t + 1, Tr - 1);             // clamped: harmless reload at the end of a run
 #pragma unroll
-            for (int p = 0; p < CHP; ++p) load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, L, pad_mode, lane);
+            for (int p = 0; p < CHP; ++p) load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, Lr, pad_mode, lane);
         }
         c32 A[CHP][NJ], B[CHP][NJ];
 #pragma unroll
@@ -199,7 +208,8 @@ __device__ __forceinline__ int pairs_tile_slot_linear(int i, int chp) {
 template <int N>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, 2) void k_stft_pairs(const float* __restrict__ x, c32* __restrict__ X,
                                                                     const float* __restrict__ win, const c32* __restrict__ tw,
-                                                                    int chans, int L, int T, int pad_mode, int runs_per_sig) {
+                                                                    int chans, int L, int T, int pad_mode, int runs_per_sig,
+                                                                    const int* __restrict__ lens, int sig_per_room) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, NJ = E / 2 + 1, EH = E / 2;
     __shared__ StftPairsShared<N> sh;
     const int wave = wave_id(), lane = threadIdx.x & 63, tid = threadIdx.x;
@@ -208,7 +218,15 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, 2) void k_stft_
     const int chp = (chans + 1) / 2;
     const long long g = blockIdx.x / runs_per_sig;
     const int t0 = (int)(blockIdx.x % runs_per_sig) * STFT_RUN;
-    const int t1 = min(T, t0 + STFT_RUN);
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / (N / 2) : T;      // see k_stft
+    if (lens) {                                    // workgroup-uniform, before the first barrier
+        for (int t = max(t0, Tr); t < min(T, t0 + STFT_RUN); ++t) {
+            c32* Xo = X + ((g * T + t) * (long long)F) * chans;
+            for (int i = tid; i < F * chans; i += 64 * STFT_WAVES) Xo[i] = make_float2(0.f, 0.f);
+        }
+        if (t0 >= Tr) return;
+    }
+    const int t1 = min(Tr, t0 + STFT_RUN);
     WaveTw<N> wtw;
     wtw.init(tw, lane);
     float w[E];
@@ -216,11 +234,11 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, 2) void k_stft_
     const float* xa = x + (g * chans + (mine ? 2 * wave : 0)) * (long long)L;
     const float* xb = two ? xa + L : xa;
     c32 raw[E];
-    load_frame_slots<N, 0, E>(raw, xa, xb, t0, L, pad_mode, lane);
+    load_frame_slots<N, 0, E>(raw, xa, xb, t0, Lr, pad_mode, lane);
     c32* tile = &sh.tile[0][0];                    // row pitch 2 * chp: the frame's X block when chans is even
     for (int t = t0; t < t1; ++t) {
         c32 nxt[EH];
-        load_frame_slots<N, EH, E>(nxt, xa, xb, min(t + 1, T - 1), L, pad_mode, lane);
+        load_frame_slots<N, EH, E>(nxt, xa, xb, min(t + 1, Tr - 1), Lr, pad_mode, lane);
         if (mine) {
             c32 v[E];
             apply_window<N>(v, raw, w, two);
@@ -280,7 +298,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_mask_ora
                                                                   float* __restrict__ mask, const float* __restrict__ win,
                                                                   const c32* __restrict__ tw, int L, int T, int pad_mode,
                                                                   int mask_type, int mask_pow, float thr_lin, int runs_per_sig,
-                                                                  long long n_witems) {
+                                                                  long long n_witems, const int* __restrict__ lens, int sig_per_room) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, EH = E / 2;
     __shared__ StftShared<N> sh;
     const int wave = wave_id(), lane = threadIdx.x & 63;
@@ -288,7 +306,15 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_mask_ora
     if (item >= n_witems) return;
     const long long g = item / runs_per_sig;
     const int t0 = (int)(item % runs_per_sig) * STFT_RUN;
-    const int t1 = min(T, t0 + STFT_RUN);
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / (N / 2) : T;      // see k_stft
+    if (lens) {                                    // the mask of a frame that does not exist is FORCED to zero ('iam' there is 0 / 0)
+        for (int t = max(t0, Tr); t < min(T, t0 + STFT_RUN); ++t) {
+            float* mo = mask + (g * T + t) * (long long)F;
+            for (int i = lane; i < F; i += 64) mo[i] = 0.f;
+        }
+        if (t0 >= Tr) return;
+    }
+    const int t1 = min(Tr, t0 + STFT_RUN);
     WaveTw<N> wtw;
     wtw.init(tw, lane);
     float w[E];
@@ -296,10 +322,10 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_mask_ora
     const float* xs = s_ref + g * (long long)L;
     const float* xn = n_ref + g * (long long)L;
     c32 raw[E];
-    load_frame_slots<N, 0, E>(raw, xs, xn, t0, L, pad_mode, lane);
+    load_frame_slots<N, 0, E>(raw, xs, xn, t0, Lr, pad_mode, lane);
     for (int t = t0; t < t1; ++t) {
         c32 nxt[EH];
-        load_frame_slots<N, EH, E>(nxt, xs, xn, min(t + 1, T - 1), L, pad_mode, lane);
+        load_frame_slots<N, EH, E>(nxt, xs, xn, min(t + 1, Tr - 1), Lr, pad_mode, lane);
         c32 v[E];
         apply_window<N>(v, raw, w, true);
         fft_wave<N>(v, wtw, sh.buf[wave], lane);
@@ -321,16 +347,29 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_mask_ora
     }
 }
 
+// element i of a [n_sig][T][F] array lies in a frame its room does not have (per-room lengths; hop = F - 1)
+__device__ __forceinline__ bool tf_beyond_room(const int* __restrict__ lens, long long i, int T, int F, int sig_per_room) {
+    const long long gt = i / F;
+    return (int)(gt % T) >= 1 + lens[(gt / T) / sig_per_room] / (F - 1);
+}
+
+// lens (per-room lengths, nullptr: none): the masks of [n_sig][T][F] arrays are forced to zero in the frames beyond a room's clip
 static __global__ void k_tf_mask(const c32* __restrict__ S, const c32* __restrict__ Nn, float* __restrict__ mask,
-                          long long n, int mask_type, int mask_pow, float thr_lin) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        mask[i] = tf_mask_value(S[i], Nn[i], mask_type, mask_pow, thr_lin);
+                          long long n, int mask_type, int mask_pow, float thr_lin, const int* __restrict__ lens, int T, int F,
+                          int sig_per_room) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float m = tf_mask_value(S[i], Nn[i], mask_type, mask_pow, thr_lin);
+        mask[i] = (lens && tf_beyond_room(lens, i, T, F, sig_per_room)) ? 0.f : m;
+    }
 }
 
 static __global__ void k_tf_mask_channel(const c32* __restrict__ S, const c32* __restrict__ Nn, float* __restrict__ mask, long long n, int M,
-                                  int ch, int mask_type, int mask_pow, float thr_lin) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        mask[i] = tf_mask_value(S[i * M + ch], Nn[i * M + ch], mask_type, mask_pow, thr_lin);
+                                  int ch, int mask_type, int mask_pow, float thr_lin, const int* __restrict__ lens, int T, int F,
+                                  int sig_per_room) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float m = tf_mask_value(S[i * M + ch], Nn[i * M + ch], mask_type, mask_pow, thr_lin);
+        mask[i] = (lens && tf_beyond_room(lens, i, T, F, sig_per_room)) ? 0.f : m;
+    }
 }
 
 // ---- iSTFT --------------------------------------------------------------------------------------------
@@ -357,7 +396,8 @@ __device__ __forceinline__ float* istft_frame(IstftShared<N>& sh, int j) {
 template <int N, bool SOLO = false>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_istft(const c32* __restrict__ Z, float* __restrict__ out,
                                                             const float* __restrict__ win, const c32* __restrict__ tw,
-                                                            int L, int T, int blocks_per_sig) {
+                                                            int L, int T, int blocks_per_sig, const int* __restrict__ lens,
+                                                            int sig_per_room) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, H = N / 2;
     constexpr int SEGS = SOLO ? STFT_WAVES - 1 : ISTFT_SEGS;
     __shared__ IstftShared<N> sh;
@@ -367,10 +407,21 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_istft(co
     wtw.init(tw, lane);
     const long long g = blockIdx.x / blocks_per_sig;
     const int seg0 = (int)(blockIdx.x % blocks_per_sig) * SEGS;             // first output segment == first frame
+    // L, T: the pitch of the arrays; Lr, Tr: the room's own clip (disco_set_lengths): its window sum is that of Tr frames, samples
+    // at and beyond Lr are exact zeros
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / H : T;
+    if (lens && seg0 >= Tr) {                      // (workgroup-uniform) nothing of this block exists: zeros, no spectrum touched
+        float* oz = out + g * (long long)L;
+        for (int i = threadIdx.x; i < SEGS * H; i += blockDim.x) {
+            const long long pos = (long long)seg0 * H + i;
+            if (pos < L) oz[pos] = 0.f;
+        }
+        return;
+    }
     const int ta = SOLO ? seg0 + wave : seg0 + 2 * wave, tb = ta + 1;
     const c32* Za = Z + (g * T + ta) * (long long)F;
     const c32* Zb = Z + (g * T + tb) * (long long)F;
-    const bool has_a = ta < T, has_b = !SOLO && tb < T;
+    const bool has_a = ta < Tr, has_b = !SOLO && tb < Tr;
     // V[n] = A~[n] + i B~[n] with A~, B~ the Hermitian extensions; the inverse transform is conj(FFT(conj V)) / N
     c32 v[E];
 #pragma unroll
@@ -413,10 +464,10 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_istft(co
         if (seg < T && pos < L) {
             const float w0 = sh.win[H + n], w1 = sh.win[n];
             float wss = w0 * w0;
-            if (seg + 1 < T) wss += w1 * w1;
+            if (seg + 1 < Tr) wss += w1 * w1;
             float val = frame(j)[H + n] + frame(j + 1)[n];
             if (wss > 1.17549435e-38f) val /= wss;
-            o[pos] = val;
+            o[pos] = (lens && pos >= Lr) ? 0.f : val;
         }
     }
 }
@@ -472,7 +523,8 @@ template <int N, int M, bool STORE = true>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M <= 4) ? DISCO_SC_WPE : 1) void k_stft_cov(const float* __restrict__ x, const float* __restrict__ mask,
                                                                c32* __restrict__ X, float4* __restrict__ part,
                                                                const float* __restrict__ win, const c32* __restrict__ tw,
-                                                               int L, int T, int pad_mode, int chunks, int runw) {
+                                                               int L, int T, int pad_mode, int chunks, int runw,
+                                                               const int* __restrict__ lens, int sig_per_room, int zero_beyond) {
     static_assert(STFT_WAVES == 4, "one bin per thread needs 4 waves for 256 bins");
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, EH = E / 2, CHP = (M + 1) / 2, MP = 2 * CHP;
     constexpr int NP = M * (M + 1) / 2;
@@ -488,7 +540,25 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
     const int c = (int)(blockIdx.x % chunks);
     const int tb = c * STFT_WAVES * runw;
     const int ts = tb + wave * runw;
-    const int te = min(T, ts + runw);
+    // L, T: the pitch of the arrays; Lr, Tr: the room's own clip (disco_set_lengths; the same without lengths).  Frames at or beyond Tr
+    // enter no sum and, stored, are exact zeros; their samples and masks are never read.
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / (N / 2) : T;
+    if (lens) {                                    // (workgroup-uniform, before the first barrier)
+        const int tz0 = max(tb, Tr), tz1 = min(T, tb + STFT_WAVES * runw);
+        // the frames of this chunk the room does not have: zeros, unless every reader of X knows the lengths itself (zero_beyond = 0: the
+        // fused route of the whole path, where X never leaves the workspace -- the zeros would cost what the spectra cost to store)
+        if (STORE && zero_beyond && tz0 < tz1) {
+            c32* Xz = X + ((g * T + tz0) * (long long)F) * M;
+            const long long nz = (long long)(tz1 - tz0) * F * M;
+            for (long long i = tid; i < nz; i += 64 * STFT_WAVES) Xz[i] = make_float2(0.f, 0.f);
+        }
+        if (tb >= Tr) {                            // a chunk wholly in the padding: zero sums, no sample or mask touched
+            float4* oz = part + ((g * chunks + c) * F) * (long long)NP;
+            for (int i = tid; i < F * NP; i += 64 * STFT_WAVES) oz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+    }
+    const int te = min(Tr, ts + runw);
     WaveTw<N> wtw;
     wtw.init(tw, lane);
     float w[E];
@@ -503,7 +573,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
     c32 raw[CHP][E];
 #pragma unroll
     for (int p = 0; p < CHP; ++p) {
-        if (ts < te) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], ts, L, pad_mode, lane);
+        if (ts < te) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], ts, Lr, pad_mode, lane);
         else {
 #pragma unroll
             for (int e = 0; e < E; ++e) raw[p][e] = make_float2(0.f, 0.f);
@@ -534,21 +604,21 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
         float mv[STFT_WAVES][BPT], mny[STFT_WAVES];
 #pragma unroll
         for (int ww = 0; ww < STFT_WAVES; ++ww) {
-            const int t2 = min(tb + ww * runw + it, T - 1);          // clamped: unconditional loads, used only when valid
+            const int t2 = min(tb + ww * runw + it, Tr - 1);         // clamped: unconditional loads, used only when valid
 #pragma unroll
             for (int b = 0; b < BPT; ++b) mv[ww][b] = (DISCO_SC_EXP & 8) ? 0.5f : mg[(long long)t2 * F + tid + 256 * b];
             mny[ww] = (DISCO_SC_EXP & 8) ? 0.5f : mg[(long long)t2 * F + F - 1];
         }
         c32 nxt[CHP][EH];
         {
-            const int tn = min(t + 1, T - 1);              // clamped: harmless reload at the end of a run
+            const int tn = min(t + 1, Tr - 1);             // clamped: harmless reload at the end of a run
 #pragma unroll
             for (int p = 0; p < CHP; ++p) {
                 if (DISCO_SC_EXP & 8) {
 #pragma unroll
                     for (int e = 0; e < EH; ++e) nxt[p][e] = make_float2(0.25f * e + lane, 1.f);
                 } else {
-                    load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, L, pad_mode, lane);
+                    load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, Lr, pad_mode, lane);
                 }
             }
         }
@@ -585,7 +655,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
 #pragma unroll
         for (int ww = 0; ww < STFT_WAVES; ++ww) {
             const int t2 = tb + ww * runw + it;
-            if (t2 < min(T, tb + (ww + 1) * runw)) {          // workgroup-uniform
+            if (t2 < min(Tr, tb + (ww + 1) * runw)) {         // workgroup-uniform
                 c32* Xo = STORE ? X + ((g * T + t2) * (long long)F) * M : nullptr;
                 if (STORE && (M & 1) == 0 && !(DISCO_SC_EXP & 4)) {
                     // even M: the tile row IS the X row (F*M complex, contiguous) -> straight 16-B-per-lane copy, every

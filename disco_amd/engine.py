@@ -84,6 +84,7 @@ class Engine:
         self.F = self.lib.disco_n_freq(self.ctx)
         self.stream = None
         self._tuning = (0, 0, 0, 0)                     # what set_tuning pinned (the library has no getter)
+        self._lengths = None                            # per-room clip lengths (set_lengths; None = the uniform batch)
         self._ctor = dict(mics=mics, length=length, n_fft=n_fft, hop=hop, ref_mic=ref_mic, mask=mask, bin_thr=bin_thr, mu=mu,
                           pad_mode=pad_mode, device=device, staged_step2=staged_step2, lazy_scratch=lazy_scratch)
         # the hipemu TEST build (tests/emu_build.py) keeps "device" memory on the host: CPU torch tensors are legitimate there
@@ -263,6 +264,32 @@ class Engine:
         self._chk(self.lib.disco_set_z_blocks(self.ctx, nodes_per_block))
         self.zblk = nodes_per_block
 
+    def set_lengths(self, lengths):
+        """Per-room clip lengths (disco_set_lengths): `lengths` holds one valid length L_r <= length per room, or is None to restore
+        the uniform batch.  The arrays keep their shapes; room r is processed as if run alone in an engine of length L_r: samples at
+        and beyond L_r are never read, frames t >= T_r = 1 + L_r / hop are exact zeros in every spectrum and computed mask, output
+        samples at and beyond L_r are exact zeros.  Masks passed in must be finite in the padding frames.  The online mode,
+        `mask_ivad` and a node shard refuse while lengths are set."""
+        if lengths is None:
+            self._chk(self.lib.disco_set_lengths(self.ctx, None, 0))
+            self._lengths = None
+            return
+        a = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int32)
+        if not np.array_equal(a, np.asarray(lengths).reshape(-1)):
+            raise ValueError('lengths must be integers')
+        self._chk(self.lib.disco_set_lengths(self.ctx, a.ctypes.data, int(a.shape[0])))
+        self._lengths = a.copy()
+
+    @property
+    def lengths(self):
+        """(R,) int32: the valid length of every room (the engine's `length` for all of them while none are set)."""
+        return np.full(self.R, self.Lsamp, np.int32) if self._lengths is None else self._lengths.copy()
+
+    @property
+    def frames(self):
+        """(R,) int32: T_r = 1 + L_r / hop, the frames room r has (the rest of the T frames of the arrays are padding)."""
+        return (1 + self.lengths // self.cfg.hop).astype(np.int32)
+
     def set_tuning(self, stft_frames_per_wave=0, cov_chunks=0, step2_chunks=0, istft_pairs=0):
         """Pin the launch geometry (0 = batch-size heuristic): lets a small batch run the code path of a large one."""
         self._chk(self.lib.disco_set_tuning(self.ctx, stft_frames_per_wave, cov_chunks, step2_chunks, istft_pairs))
@@ -270,18 +297,22 @@ class Engine:
 
     OPTION_KEYS = ('room_cov', 'overlap_solves', 'solve_thread', 'solve_dpp', 'online_sq32', 'fuse_wide_istft')
 
-    def sibling(self, rooms):
+    def sibling(self, rooms, first_room=0):
         """A second engine for `rooms` rooms of the same problem: every field of the configuration (hop, reference microphone, mask
         settings, mu, padding, flags), the node shard and the layout of the exchanged signals are this engine's; options, tuning and
-        stream follow with `follow(parent)`."""
+        stream follow with `follow(parent)`.  Per-room lengths: the sibling takes those of rooms [first_room, first_room + rooms)."""
         kid = Engine(rooms=rooms, nodes=self.K, lib=self.lib, **self._ctor)
         if (self.k0, self.Kl) != (0, self.K):
             kid.set_node_shard(self.k0, self.Kl)
-        kid.follow(self)
+        kid.follow(self, first_room)
         return kid
 
-    def follow(self, parent):
-        """Take over `parent`'s route options, pinned launch geometry and stream (idempotent; a few host calls)."""
+    def follow(self, parent, first_room=0):
+        """Take over `parent`'s route options, pinned launch geometry, stream and (its slice of the) per-room lengths (idempotent; a
+        few host calls)."""
+        mine = None if parent._lengths is None else parent._lengths[first_room:first_room + self.R]
+        if (mine is None) != (self._lengths is None) or (mine is not None and not np.array_equal(mine, self._lengths)):
+            self.set_lengths(mine)
         for key in self.OPTION_KEYS:
             v = parent.get_option(key)
             if self.get_option(key) != v:

@@ -12,6 +12,10 @@ clipping / importance-weight arithmetic of the reference is applied to those.
     third_octave_filterbank   sigproc_utils.py:90-116
 
 `start` / `stop` select the scored span; the reference scores [fs : min_len] (tango.py:541-593), i.e. start = 16000.
+Batches with per-room lengths (Engine.set_lengths): the enhanced signals are exact zeros beyond each room's clip, so the metrics
+that score non-zero samples or inner products (snr, delta_snr, sd, si_sdr, si_bss) need nothing.  fw_snr / fw_sd do NOT handle a
+mixed batch: the band filters ring past the end of a clip, so their non-zero-sample rule would score that tail; they need a
+`start` / `stop` per signal -- call them per group of rooms of one length.
 Band edges: the reference takes them from python-acoustics' OctaveBand (third-party, absent); they are restated from
 IEC 61260-1 (base-10 octave ratio, exact mid-band frequencies) -- the one unpinned piece, see oracle/metrics_oracle.py.
 """

@@ -66,7 +66,7 @@ def _get_mask(eng, Sh_c, Nh_c, ts, vad, mod=None, Yh_c=None, z_rows=None):
     return eng.tf_mask(np.ascontiguousarray(Sh_c), np.ascontiguousarray(Nh_c), type=vad).numpy().astype(np.float32)
 
 
-def _time_mask(eng, vad, s_ch, n_ch, y_ch=None, mod=None, z_rows=None, n_fft=N_FFT, pad_mode='reflect'):
+def _time_mask(eng, vad, s_ch, n_ch, y_ch=None, mod=None, z_rows=None, n_fft=N_FFT, pad_mode='reflect', lengths=None):
     """A mask the library does not compute by itself inside disco_tango_reference, as a device array (R, K, T, F):
     'ivad' (frame VAD of the target image's time signal, tango.py:217-221), a TF mask of ANOTHER type than the engine's
     (step 2 with vads[1] != vads[0]), or the CRNN's prediction from |STFT(y_ch)| [+ |z| of the other nodes]."""
@@ -84,17 +84,25 @@ def _time_mask(eng, vad, s_ch, n_ch, y_ch=None, mod=None, z_rows=None, n_fft=N_F
             m = mod.predict_masks(torch.from_numpy(np.ascontiguousarray(mag)).to(par.device, par.dtype))
         return np.ascontiguousarray(m.float().cpu().numpy().reshape(R, K, eng.T, eng.F))
     other = get_engine(rooms=R, nodes=K, mics=1, length=L, n_fft=n_fft, mask=vad, pad_mode=pad_mode)
-    return other.mask_oracle(np.ascontiguousarray(s_ch.reshape(R * K, L)), np.ascontiguousarray(n_ch.reshape(R * K, L))).numpy() \
-        .reshape(R, K, eng.T, eng.F)
+    try:                                                                       # (a cached engine: the lengths do not outlive the call)
+        other.set_lengths(lengths)
+        return other.mask_oracle(np.ascontiguousarray(s_ch.reshape(R * K, L)), np.ascontiguousarray(n_ch.reshape(R * K, L))).numpy() \
+            .reshape(R, K, eng.T, eng.F)
+    finally:
+        other.set_lengths(None)
 
 
 def offline_tango_batched(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_sigs='zs_hat', n_fft=N_FFT,
-                          pad_mode='reflect', ref_mic=0, mu=1.0, steps=3):
+                          pad_mode='reflect', ref_mic=0, mu=1.0, steps=3, lengths=None):
     """y, s, n: (R, K, M, L) float32.  Returns a dict of device-computed arrays with a leading room axis, in the
     engine's frame-major layout (R, K, T, F): yf, sf, nf, z_y, z_s, z_n, zn, masks_z, mask_w (steps=1: the step-1 five).
     The whole path is ONE library call (disco_tango_reference: STFTs, masks, statistics, solves, every mask_for_z variant and
-    the three filter passes stay on the device); only 'ivad' / DNN masks are prepared outside it and passed in."""
+    the three filter passes stay on the device); only 'ivad' / DNN masks are prepared outside it and passed in.
+    lengths: (R,) valid samples per room (Engine.set_lengths): room r comes out as if it had been run alone at L = lengths[r]; the
+    frames beyond its T_r = 1 + lengths[r] / hop are zeros in every returned array.  TF mask types only."""
     vads = _mask_names(vads, mods)
+    if lengths is not None and any(v in ('ivad', 'crnn') for v in vads):
+        raise NotImplementedError("per-room lengths with 'ivad' / 'crnn' masks: only the TF mask types take lengths")
     mods = [None, None] if mods is None else list(mods) + [None] * (2 - len(mods))
     MODES = ('local', None, 'distant', 'compressed', 'use_oracle_refs', 'use_oracle_zs', 'previous')
     if mask_for_z not in MODES:
@@ -107,6 +115,17 @@ def offline_tango_batched(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_
         raise NotImplementedError("mask_for_z='compressed' needs a TF mask type at step 1 (the reference passes neither a time signal nor z to get_mask there, tango.py:403)")
     eng = get_engine(rooms=R, nodes=K, mics=M, length=L, n_fft=n_fft, mask=_engine_mask_type(vads[0]), pad_mode=pad_mode,
                      ref_mic=ref_mic, mu=mu, staged_step2=True)
+    if lengths is None:
+        return _tango_batched_on(eng, y, s, n, vads, mods, mask_for_z, z_sigs, n_fft, pad_mode, ref_mic, steps, None)
+    try:                                                                       # (a cached engine: the lengths do not outlive the call)
+        eng.set_lengths(lengths)
+        return _tango_batched_on(eng, y, s, n, vads, mods, mask_for_z, z_sigs, n_fft, pad_mode, ref_mic, steps, eng.lengths)
+    finally:
+        eng.set_lengths(None)
+
+
+def _tango_batched_on(eng, y, s, n, vads, mods, mask_for_z, z_sigs, n_fft, pad_mode, ref_mic, steps, lengths):
+    R, K, M, L = y.shape
     tf = lambda v: v[:-1] in ('irm', 'ibm', 'iam')
     # masks the library cannot derive from (S, N) with the engine's own TF type (see _time_mask); None = computed inside
     mz = None if tf(vads[0]) else _time_mask(eng, vads[0], s[:, :, ref_mic], n[:, :, ref_mic], y[:, :, ref_mic], mods[0],
@@ -130,7 +149,7 @@ def offline_tango_batched(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_
     elif vads[1] == vads[0] and ref_mic == 0:
         mw = mz                                                                # 'ivad' twice on the same channel
     else:
-        mw = _time_mask(eng, vads[1], s[:, :, 0], n[:, :, 0], n_fft=n_fft, pad_mode=pad_mode)
+        mw = _time_mask(eng, vads[1], s[:, :, 0], n[:, :, 0], n_fft=n_fft, pad_mode=pad_mode, lengths=lengths)
     if need_z_for_mw:
         out.update({k: v.numpy() for k, v in eng.tango_reference(yd, sd, nd, mask_z=mz, mask_w=mw, mask_for_z=mask_for_z, steps=2).items()})
         return out
@@ -237,3 +256,32 @@ def offline_tango(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_sigs='zs
     d = offline_tango_batched(yb, sb, nb, vads=vads, mods=mods, mask_for_z=mask_for_z, z_sigs=z_sigs)
     K = d['yf'].shape[1]
     return tuple([np.ascontiguousarray(d[nm][0, k].T) for k in range(K)] for nm in names)
+
+
+def offline_tango_rooms(rooms, vads='irm1', mask_for_z=MASK_Z, n_fft=N_FFT, pad_mode='reflect', ref_mic=0, mu=1.0):
+    """`offline_tango` for a list of rooms whose clips differ in length, in ONE batched call: `rooms` is a list of (y, s, n), each in
+    the reference's [node][channel] -> time form, all with the same node and channel counts.  Returns a list with the reference's
+    9-tuple of every room, (yf, sf, nf, z_y, z_s, z_n, zn, masks_z, mask_w), each a list over nodes of (F, T_r) arrays with
+    T_r = 1 + L_r / hop: what `offline_tango` returns for that room alone."""
+    names = ['yf', 'sf', 'nf', 'z_y', 'z_s', 'z_n', 'zn', 'masks_z', 'mask_w']
+    trip = []
+    for r, room in enumerate(rooms):
+        b = [_as_batch(x) for x in room]
+        if any(x is None for x in b) or len({x.shape for x in b}) != 1:
+            raise ValueError(f'room {r}: y, s, n must have the same (nodes, channels, samples) shape, uniform over the nodes')
+        if trip and b[0].shape[1:3] != trip[0][0].shape[1:3]:
+            raise ValueError(f'rooms differ in (nodes, channels): {trip[0][0].shape[1:3]} (room 0) and {b[0].shape[1:3]} (room {r}); '
+                             'group the rooms by shape')
+        trip.append(b)
+    if not trip:
+        return []
+    lengths = np.array([b[0].shape[-1] for b in trip], np.int32)
+    R, (K, M), Lmax = len(trip), trip[0][0].shape[1:3], int(lengths.max())
+    ysn = np.zeros((3, R, K, M, Lmax), np.float32)
+    for r, b in enumerate(trip):
+        for i in range(3):
+            ysn[i, r, :, :, :lengths[r]] = b[i][0]
+    d = offline_tango_batched(ysn[0], ysn[1], ysn[2], vads=vads, mask_for_z=mask_for_z, n_fft=n_fft, pad_mode=pad_mode, ref_mic=ref_mic,
+                              mu=mu, lengths=lengths)
+    frames = 1 + lengths // (n_fft // 2)
+    return [tuple([np.ascontiguousarray(d[nm][r, k, :frames[r]].T) for k in range(K)] for nm in names) for r in range(R)]

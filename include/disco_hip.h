@@ -120,6 +120,29 @@ int  disco_set_node_shard(disco_ctx* ctx, int first_node, int node_count);
  * default.  Outputs (z written by disco_apply for the LOCAL nodes) keep [R][count][T][F]: that IS a rank's block. */
 int  disco_set_z_blocks(disco_ctx* ctx, int nodes_per_block);
 
+/* Per-room clip lengths: rooms of different durations in one batch.  The arrays keep their rectangular shapes ([R][K][M][cfg.length],
+ * [R][K][T][F] with T = disco_n_frames, which does not change); room r is processed as if it had been run alone in a context of
+ * length = lengths[r], with T_r = 1 + lengths[r] / hop frames:
+ *   - samples at and beyond lengths[r] are never read (they may hold anything, NaN included): the transform reflects or zero-pads at
+ *     lengths[r];
+ *   - frames t >= T_r do not exist: they enter no statistic; spectra, z, yf and the masks the library computes are exact zeros there.
+ *     Masks the CALLER passes in must be FINITE in those frames (their values do not matter);
+ *   - output samples n < lengths[r] are the inverse transform with the window sum of T_r frames, n >= lengths[r] exact zeros;
+ *   - disco_cov_masked / disco_stft_cov_fused, when they return matrices, divide room r's sums by T_r.
+ * lengths: HOST array of cfg.rooms int32 (copied; the context owns the device copy, allocated here and never inside a compute call),
+ * or NULL to restore the uniform batch.  pad_mode reflect: n_fft/2 < lengths[r] <= cfg.length (the rule disco_create applies to
+ * cfg.length); constant: 1 <= lengths[r] <= cfg.length.  Otherwise DISCO_E_ARG, state unchanged.  lengths[r] == cfg.length for every r
+ * gives bit for bit the results of the uniform batch.  A second call rewrites the same device block in place (the kernels read the
+ * lengths from device memory; launch geometry and workspace sizes do not depend on them), so a hipGraph captured with lengths set
+ * replays with the lengths in force at replay.
+ * Covered: disco_stft, disco_istft, disco_mask_oracle (signal g of n_sig belongs to room g / (n_sig / cfg.rooms); n_sig not a multiple
+ * of cfg.rooms is DISCO_E_ARG while lengths are set), disco_cov_masked, disco_stft_cov_fused, disco_step2_*_fused,
+ * disco_apply_istft_fused, and every route of disco_tango_enhance, disco_tango_enhance_iterated and disco_tango_reference.
+ * Refused with DISCO_E_UNSUPPORTED while lengths are set: disco_online_mwf, disco_tango_online, disco_tango_online_stream,
+ * disco_mask_ivad, a node shard (disco_set_node_shard; and disco_set_lengths while a shard is active).  disco_tf_mask is element-wise and
+ * knows no frames: it computes every element it is given. */
+int  disco_set_lengths(disco_ctx* ctx, const int32_t* lengths, int n_rooms);
+
 /* Launch geometry.  By default every kernel derives its work split from the batch size (long per-wave frame runs and single
  * covariance chunks once R*K fills the chip, short runs and up to 8 chunks for small batches).  This call pins it, so that a
  * SMALL batch can be run -- and checked against the oracle -- on exactly the code path a large production batch takes:
