@@ -212,6 +212,75 @@ class Engine:
             self._chk(self.lib.disco_band_stats(self.ctx, px, n_sig, L, start, stop, pb, pa, b.shape[0], st.ptr, self.stream))
         return st
 
+    def lag_corr(self, a, b, lag_lo, lag_hi, start=0, stop=None):
+        """a, b (n_pair, L) float32 -> (n_pair, lag_hi - lag_lo + 1) float64: c[i][t - lag_lo] = sum_n a[i][n] b[i][n + t] over the n with
+        n and n + t inside [start, stop); lags within +-511  (disco_lag_corr)."""
+        if len(a.shape) != 2 or tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f'a and b must both be (n_pair, L): {tuple(a.shape)} and {tuple(b.shape)}')
+        n_pair, L = (int(v) for v in a.shape)
+        stop = L if stop is None else stop
+        nlag = int(lag_hi) - int(lag_lo) + 1
+        pa, ka = self.to_device(a, np.float32)
+        pb, kb = (pa, ka) if b is a else self.to_device(b, np.float32)
+        wsb = int(self.lib.disco_lag_corr_workspace_bytes(self.ctx, n_pair, L, max(nlag, 1)))
+        ws = self.empty((max(wsb, 8) // 8,), np.float64)
+        out = self.empty((n_pair, max(nlag, 1)), np.float64)
+        self._chk(self.lib.disco_lag_corr(self.ctx, pa, pb, n_pair, L, start, stop, lag_lo, lag_hi, out.ptr, ws.ptr, ws.nbytes, self.stream))
+        return out
+
+    BSS_WORKSPACE_BUDGET = 1 << 30      # bytes of factor / correlation workspace one disco_bss_eval call of Engine.bss_eval may take
+
+    def bss_eval(self, refs, ests, start=0, stop=None, flen=512, all_pairs=False, budget_bytes=None):
+        """BSS-eval energies (disco_bss_eval): refs (n_set, nsrc, L), ests (n_set, n_est, nsrc, L) float32 -> (energies, status), NumPy:
+        energies (n_set, n_est, nsrc, 4), estimate i against source i, or (n_set, n_est, nsrc, nsrc, 4) with all_pairs, estimate i against
+        source j -- each {p_j, p_all, ee, status}; status (n_set,) int32, non-zero where the set's Gram matrix is singular to working
+        precision (its energies are NaN).  A large batch is walked in chunks of sets whose workspace stays under `budget_bytes` (default
+        BSS_WORKSPACE_BUDGET; 10 MB of factors per two-source set at flen 512, so about 100 sets per chunk); the chunking does not
+        change a bit of the result.  NumPy inputs are copied chunk by chunk; device-resident tensors / DevBufs are read in place."""
+        rs, es = tuple(int(v) for v in refs.shape), tuple(int(v) for v in ests.shape)
+        if len(rs) != 3 or len(es) != 4 or es[0] != rs[0] or es[2:] != rs[1:]:
+            raise ValueError(f'refs must be (n_set, nsrc, L) and ests (n_set, n_est, nsrc, L): {rs} and {es}')
+        n_set, nsrc, L = rs
+        n_est = es[1]
+        if min(n_set, nsrc, L, n_est) < 1:
+            raise ValueError(f'empty batch: refs {rs}, ests {es}')
+        stop = L if stop is None else stop
+        flen = int(flen)
+        per_set = int(self.lib.disco_bss_workspace_bytes(self.ctx, 1, nsrc, flen, L))
+        if per_set == 0:                                  # outside the supported range: the library names the limit, nothing is launched
+            self._chk(self.lib.disco_bss_eval(self.ctx, None, None, n_set, nsrc, n_est, L, start, stop, flen, int(all_pairs), None, None, None, 0, self.stream))
+            raise DiscoError('disco_bss_eval: unsupported shape')
+        budget = self.BSS_WORKSPACE_BUDGET if budget_bytes is None else int(budget_bytes)
+        step = max(1, min(n_set, budget // per_set))
+        wsb = int(self.lib.disco_bss_workspace_bytes(self.ctx, step, nsrc, flen, L))
+        ws = self.empty((wsb // 8 + 1,), np.float64)
+        oshape = (nsrc, nsrc, 4) if all_pairs else (nsrc, 4)
+        energies = np.empty((n_set, n_est) + oshape, np.float64)
+        status = np.empty((n_set,), np.int32)
+        host = isinstance(refs, np.ndarray), isinstance(ests, np.ndarray)
+        pr0 = pe0 = None
+        if not host[0]:
+            pr0, kr = self.to_device(refs, np.float32)
+        if not host[1]:
+            pe0, ke = self.to_device(ests, np.float32)
+        for i0 in range(0, n_set, step):
+            n = min(step, n_set - i0)
+            if host[0]:
+                pr, kr_ = self.to_device(refs[i0:i0 + n], np.float32)
+            else:
+                pr = pr0 + 4 * i0 * nsrc * L
+            if host[1]:
+                pe, ke_ = self.to_device(ests[i0:i0 + n], np.float32)
+            else:
+                pe = pe0 + 4 * i0 * n_est * nsrc * L
+            out = self.empty((n, n_est) + oshape, np.float64)
+            st = self.empty((n,), np.int32)
+            self._chk(self.lib.disco_bss_eval(self.ctx, pr, pe, n, nsrc, n_est, L, start, stop, flen, int(all_pairs), out.ptr, st.ptr, ws.ptr,
+                                              ws.nbytes, self.stream))
+            energies[i0:i0 + n] = out.numpy()
+            status[i0:i0 + n] = st.numpy()
+        return energies, status
+
     def selftest_pk(self, a, b, c):
         """a, b, c (n,) complex64 -> (out_hw, out_ref), each (n, 23) complex64: the packed complex operations of
         csrc/pk.h through the v_pk_* instruction forms and through their C++ statement (include/disco_hip.h)."""

@@ -9,6 +9,8 @@ clipping / importance-weight arithmetic of the reference is applied to those.
     fw_snr, fw_sd             metrics.py:63-128, 211-279   (third-octave Butterworth bank, clip, band-importance weights)
     si_sdr                    metrics.py:342-391
     si_bss                    metrics.py:282-340      (SI-SDR / SI-SIR / SI-SAR against n_src references)
+    bss_eval_sources          mir_eval.separation.bss_eval_sources as tango.py:541-567 calls it (SDR / SIR / SAR through a 512-tap
+                              filtered projection; third-party and absent here: restated from its definition, csrc/k_bss.h)
     third_octave_filterbank   sigproc_utils.py:90-116
 
 `start` / `stop` select the scored span; the reference scores [fs : min_len] (tango.py:541-593), i.e. start = 16000.
@@ -19,6 +21,8 @@ mixed batch: the band filters ring past the end of a clip, so their non-zero-sam
 Band edges: the reference takes them from python-acoustics' OctaveBand (third-party, absent); they are restated from
 IEC 61260-1 (base-10 octave ratio, exact mid-band frequencies) -- the one unpinned piece, see oracle/metrics_oracle.py.
 """
+import itertools
+
 import numpy as np
 import scipy.signal
 
@@ -111,6 +115,82 @@ def si_bss(estimated_signal, targets, j, scaling=True, start=0, stop=None):
     artif = Snn - interf                                                      # |e_res - e_interf|^2
     f = lambda x: (10 * np.log10(x)).reshape(lead)
     return f(Sss / Snn), f(Sss / interf), f(Sss / artif)
+
+
+def _safe_db(num, den):
+    """10 log10(num / den), +inf where den == 0 (mir_eval's _safe_db)."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(den == 0, np.inf, 10 * np.log10(num / np.where(den == 0, 1.0, den)))
+
+
+def _figures(en):
+    """Engine.bss_eval energies (..., 4) = {p_j, p_all, ee, status} -> (sdr, sir, sar), each (...): mir_eval's arithmetic; NaN energies
+    (a refused set) give NaN."""
+    pj, pall, ee = en[..., 0], en[..., 1], en[..., 2]
+    nan = np.isnan(pj) | np.isnan(pall) | np.isnan(ee)
+    pj, pall, ee = (np.where(nan, 1.0, v) for v in (pj, pall, ee))
+    with np.errstate(divide='ignore'):
+        sdr = _safe_db(pj, np.maximum(ee - pj, 0.0))
+        sir = _safe_db(pj, np.maximum(pall - pj, 0.0))
+        sar = _safe_db(pall, np.maximum(ee - pall, 0.0))
+    return tuple(np.where(nan, np.nan, v) for v in (sdr, sir, sar))
+
+
+def _raise_on_zero_reference(refs, status, start=0, stop=None, lead=None):
+    """refs (n_set, nsrc, L), status of Engine.bss_eval: ValueError naming the first all-zero reference of a refused set, if there is one."""
+    if not np.any(status != 0):
+        return
+    n_set, nsrc, L = (int(v) for v in refs.shape)
+    r2 = refs.reshape(n_set * nsrc, L)
+    e_ref = _engine().pair_stats(r2, r2, start, stop).numpy()[:, 2]
+    zero = np.flatnonzero(e_ref == 0)
+    if zero.size:
+        i = int(zero[0])
+        where = tuple(int(v) for v in np.unravel_index(i // nsrc, lead)) if lead else (i // nsrc,)
+        raise ValueError(f'reference source {i % nsrc} of set {where} is all zero over the scored span')
+
+
+def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=True, start=0, stop=None, flen=512):
+    """mir_eval.separation.bss_eval_sources (name, argument order, default): -> (sdr, sir, sar, perm).
+    reference_sources, estimated_sources: (nsrc, L) as in mir_eval -> four (nsrc,) arrays, or (..., nsrc, L) batched over the leading
+    axes -> (..., nsrc); NumPy arrays (copied) or device-resident (n_set, nsrc, L) tensors (read in place).  nsrc <= 4, flen <= 512.
+    The estimate is projected on the `flen` delayed copies of its target reference (energy p_j) and on those of all references (p_all),
+    through the lag correlations, one Cholesky factorisation per reference set and a forward substitution per estimate on the GPU
+    (Engine.bss_eval); the arithmetic below on three float64 energies per figure is mir_eval's:
+        SDR = 10 log10(p_j / (ee - p_j))   SIR = 10 log10(p_j / (p_all - p_j))   SAR = 10 log10(p_all / (ee - p_all))
+    with the differences clamped at 0 from below and +inf for a zero denominator.  compute_permutation=True scores every (estimate,
+    source) pair and returns, per source j, the figures of estimate perm[j] for the permutation with the best mean SIR; False (what
+    tango.py passes) scores estimate j against source j and returns perm = arange(nsrc).
+    `start` / `stop` select the scored span.  A batch of different clip lengths needs nothing: samples past a room's clip are exact
+    zeros in references and estimates alike and add nothing to any sum.
+    An all-zero reference raises ValueError naming the signal.  Where the references of a set are linearly dependent, or their Gram
+    matrix is singular to working precision, that set's figures are NaN (mir_eval falls back to a least-squares solve there)."""
+    refs, ests = reference_sources, estimated_sources
+    if isinstance(refs, np.ndarray) or not hasattr(refs, 'data_ptr'):
+        refs = np.ascontiguousarray(refs, dtype=np.float32)
+    if isinstance(ests, np.ndarray) or not hasattr(ests, 'data_ptr'):
+        ests = np.ascontiguousarray(ests, dtype=np.float32)
+    shape = tuple(int(v) for v in refs.shape)
+    if len(shape) < 2 or tuple(int(v) for v in ests.shape) != shape:
+        raise ValueError(f'reference_sources and estimated_sources must have one shape (..., nsrc, L): {shape} and {tuple(ests.shape)}')
+    lead, nsrc, L = shape[:-2], shape[-2], shape[-1]
+    n_set = int(np.prod(lead, dtype=np.int64))
+    eng = _engine()
+    r3 = refs.reshape(n_set, nsrc, L)
+    en, status = eng.bss_eval(r3, ests.reshape(n_set, 1, nsrc, L), start, stop, flen, all_pairs=bool(compute_permutation))
+    _raise_on_zero_reference(r3, status, start, stop, lead)
+    sdr, sir, sar = _figures(en[:, 0])                                    # (n_set, nsrc[, nsrc])
+    idx = np.arange(nsrc)
+    if compute_permutation:                                               # [estimate][source], as mir_eval's sdr[jest, jtrue]
+        perms = np.array(list(itertools.permutations(range(nsrc))))
+        mean_sir = np.stack([sir[:, p, idx].mean(axis=1) for p in perms], axis=1)          # (n_set, n_perm)
+        best = np.argmax(np.where(np.isnan(mean_sir), -np.inf, mean_sir), axis=1)
+        perm = perms[best]                                                # (n_set, nsrc)
+        rows = np.arange(n_set)[:, None]
+        sdr, sir, sar = sdr[rows, perm, idx], sir[rows, perm, idx], sar[rows, perm, idx]
+    else:
+        perm = np.broadcast_to(idx, (n_set, nsrc)).copy()
+    return tuple(v.reshape(lead + (nsrc,)) for v in (sdr, sir, sar, perm))
 
 
 def band_importance(fs):

@@ -9,6 +9,10 @@
 The reference writes the audio with `soundfile.write(path, data, fs)` (third-party, absent): for a '.wav' path and float
 input that is 16-bit PCM, full scale at +-1.0.  Here the standard library's `wave` module writes the same container
 (samples = round(clip(x, -1, 1 - 2^-15) * 32768)); bit-level equality with libsndfile's rounding is not pinned.
+
+And the two result pickles of tango.py:617-635 (`room_results`, `write_result_pickles`): the level metrics and, given the mixture and
+the two enhanced mixtures in time, the eleven BSS-eval keys (SDR / SIR / SAR, what the reference takes from mir_eval), all scored on
+the GPU by disco_amd.metrics; the STOI keys (pystoi) hold NaN.
 """
 import os
 import wave
@@ -69,25 +73,35 @@ def write_room_results(root, i_rir, noise, signals, masks_z=None, mask_w=None, f
 # ---- the result pickles (tango.py:617-635) ------------------------------------------------------------------------------------
 # Two dictionaries of per-node arrays per (room, noise): `results_tango_<rir>_<noise>.p` (step-2 output) and
 # `results_mwf_<rir>_<noise>.p` (the compressed signal after step 1), same keys as the reference.  The level metrics (fw_snr,
-# fw_sd: the reference's own disco_theque/metrics.py) are computed by disco_amd.metrics on the GPU; the keys the reference fills
-# from mir_eval.separation.bss_eval_sources and pystoi.stoi (third-party, absent here) are present and hold NaN, so that code
-# reading the pickles finds every key it expects.
+# fw_sd: the reference's own disco_theque/metrics.py) are computed by disco_amd.metrics on the GPU.  The eleven keys the reference
+# fills from mir_eval.separation.bss_eval_sources (BSS_KEYS) are computed on the GPU too, by disco_amd.metrics.bss_eval_sources
+# (restated from the definition of BSS-eval; mir_eval itself is third-party and absent), when room_results is given the time
+# signals they need (y_in, sh_t, szh_t); without them they hold NaN.  The keys filled from pystoi.stoi (third-party, absent: the
+# delta_stoi* keys) are present and always hold NaN, so that code reading the pickles finds every key it expects.
 RESULT_KEYS_TANGO = ('snr_in_raw', 'sar_cnv', 'sir_cnv', 'sdr_cnv', 'delta_stoi_cnv', 'delta_stoi_dry', 'snr_out', 'snr_in_cnv',
                      'snr_in_dry', 'fw_sd_cnv', 'fw_sd_dry', 'sar_dry', 'sir_dry', 'sdr_dry', 'sdr_in_cnv', 'sir_in_cnv',
                      'sdr_in_dry', 'sir_in_dry', 'sar_in_dry')
 RESULT_KEYS_MWF = tuple('delta_stoi' if k == 'delta_stoi_cnv' else k for k in RESULT_KEYS_TANGO)
 THIRD_PARTY_KEYS = ('sar_cnv', 'sir_cnv', 'sdr_cnv', 'delta_stoi_cnv', 'delta_stoi', 'delta_stoi_dry', 'sar_dry', 'sir_dry', 'sdr_dry',
                     'sdr_in_cnv', 'sir_in_cnv', 'sdr_in_dry', 'sir_in_dry', 'sar_in_dry')
+BSS_KEYS = tuple(k for k in THIRD_PARTY_KEYS if 'stoi' not in k)
 
 
-def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS):
-    """The two result dictionaries of one (room, noise) (tango.py:541-635, the parts that are the reference's own code).
+def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
+                 bss_flen=512):
+    """The two result dictionaries of one (room, noise) (tango.py:541-635).
     s_in, n_in (K, L): target / noise images at every node's first microphone; sf_t, nf_t (K, L): their step-2 outputs in time;
     szf_t, nzf_t (K, L): their compressed (step-1) versions in time; rnd_snrs: the drawn input SNRs; s_dry, n_dry (L,): the dry
-    sources, or None (the `_dry` level metrics are then NaN too).  The first second is skipped as in the reference ([fs:])."""
+    sources, or None (the `_dry` metrics are then NaN).  The first second is skipped as in the reference ([fs:]).
+    y_in, sh_t, szh_t (K, L): the mixture at every node's first microphone, the step-2 output and the step-1 output in time.  When all
+    three are given, the eleven BSS-eval keys (BSS_KEYS) are filled as tango.py:541-567 fills them: references (s_in[k], n_in[k]) for the
+    `_cnv` keys and (s_dry, n_dry) for the `_dry` ones; estimates (sh, y - sh) for `res`, (szh, y - szh) for `resz`, (y, y - sh) for the
+    `_in_` keys of both; source 0's figures; compute_permutation=False; a `bss_flen`-tap filter (mir_eval's 512).  The differences are
+    formed in float64 and rounded to float32 once, which is what the kernels read.  Without them those keys hold NaN."""
     from .. import metrics as dm
     K = np.shape(s_in)[0]
-    L = min(np.shape(a)[-1] for a in (s_in, n_in, sf_t, nf_t, szf_t, nzf_t) if a is not None)
+    bss = y_in is not None and sh_t is not None and szh_t is not None
+    L = min(np.shape(a)[-1] for a in (s_in, n_in, sf_t, nf_t, szf_t, nzf_t) + ((y_in, sh_t, szh_t) if bss else ()) if a is not None)
     if s_dry is not None:
         L = min(L, len(s_dry), len(n_dry))
     cut = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float32)[..., fs:L])
@@ -108,6 +122,31 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
         rep = np.repeat(sd_, K, axis=0)
         res['fw_sd_dry'] = np.asarray(dm.fw_sd(cut(sf_t), rep, fs)[1])                 # :591
         resz['fw_sd_dry'] = np.asarray(dm.fw_sd(cut(szf_t), rep, fs)[1])               # :593
+    if bss:
+        cut64 = lambda a: np.asarray(a, dtype=np.float32)[..., fs:L].astype(np.float64)
+        y, sh, szh = cut64(y_in), cut64(sh_t), cut64(szh_t)
+        f32 = lambda a: a.astype(np.float32)
+        # (K, 3, 2, L'): ests (:547), ests_z (:548), ests_i (:549) of every node
+        ests = np.stack([np.stack([f32(sh), f32(y - sh)], 1), np.stack([f32(szh), f32(y - szh)], 1), np.stack([f32(y), f32(y - sh)], 1)], 1)
+
+        def figures(refs, est):
+            """refs (n_set, 2, L'), est (n_set, n_est, 2, L') -> sdr, sir, sar of source 0, each (n_set, n_est)."""
+            en, status = dm._engine().bss_eval(refs, est, flen=bss_flen)
+            dm._raise_on_zero_reference(refs, status)
+            return tuple(v[..., 0] for v in dm._figures(en))
+
+        sdr, sir, sar = figures(np.stack([cut(s_in), cut(n_in)], 1), ests)                 # :562-564
+        res['sdr_cnv'], res['sir_cnv'], res['sar_cnv'] = sdr[:, 0], sir[:, 0], sar[:, 0]
+        resz['sdr_cnv'], resz['sir_cnv'], resz['sar_cnv'] = sdr[:, 1], sir[:, 1], sar[:, 1]
+        res['sdr_in_cnv'] = resz['sdr_in_cnv'] = sdr[:, 2]                                 # :567
+        res['sir_in_cnv'] = resz['sir_in_cnv'] = sir[:, 2]
+        if s_dry is not None:                                                              # :552-560: one reference set, 3 K estimate sets
+            sdr, sir, sar = (v.reshape(K, 3) for v in figures(np.stack([cut(s_dry), cut(n_dry)], 0)[None], ests.reshape(1, 3 * K, 2, -1)))
+            res['sdr_dry'], res['sir_dry'], res['sar_dry'] = sdr[:, 0], sir[:, 0], sar[:, 0]
+            resz['sdr_dry'], resz['sir_dry'], resz['sar_dry'] = sdr[:, 1], sir[:, 1], sar[:, 1]
+            res['sdr_in_dry'] = resz['sdr_in_dry'] = sdr[:, 2]
+            res['sir_in_dry'] = resz['sir_in_dry'] = sir[:, 2]
+            res['sar_in_dry'] = resz['sar_in_dry'] = sar[:, 2]
     return res, resz
 
 

@@ -515,6 +515,36 @@ int disco_band_stats(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len,
 int disco_band_stats_gated(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, int stop,
                            const double* b, const double* a, int n_bands, double* stats, disco_stream s);
 
+/* ---- BSS-eval SDR / SIR / SAR (what tango.py:541-567 takes from mir_eval.separation.bss_eval_sources) ---------------
+ * Restated from its definition (Vincent, Gribonval, Fevotte 2006): the estimate is projected on the flen delayed copies of
+ * the target reference and on those of all nsrc references; every figure is a function of lag correlations only.
+ *
+ * disco_lag_corr: for each of n_pair signal pairs (rows of `len` floats) and every lag t in [lag_lo, lag_hi] (within +-511):
+ *   out[i][t - lag_lo] = sum_n a[i][n] b[i][n + t]   over the n with n and n + t inside [start, stop)   (float64; the products
+ *   of float32 samples are exact).  workspace: at least disco_lag_corr_workspace_bytes(ctx, n_pair, len, lag_hi - lag_lo + 1)
+ *   (per-chunk partial sums, added in chunk order: bit-identical from run to run, and per pair whatever else is in the batch). */
+size_t disco_lag_corr_workspace_bytes(const disco_ctx* ctx, int64_t n_pair, int64_t len, int n_lag);
+int disco_lag_corr(disco_ctx* ctx, const float* a, const float* b, int64_t n_pair, int64_t len, int start, int stop, int lag_lo,
+                   int lag_hi, double* out, void* workspace, size_t workspace_bytes, disco_stream s);
+
+/* disco_bss_eval: refs [n_set][nsrc][len], ests [n_set][n_est][nsrc][len] float (the n_est estimate sets of a reference set
+ * share its factorisation), scored over [start, stop) with a flen-tap filter; 1 <= nsrc <= 4, 1 <= flen <= 512
+ * (DISCO_E_UNSUPPORTED beyond).  With G the (nsrc flen)^2 block-Toeplitz Gram matrix of the delayed references and d its
+ * right-hand side for an estimate e:  p_j = d_j^T G_jj^-1 d_j,  p_all = d^T G^-1 d,  ee = sum e^2, and
+ *   all_pairs == 0: out[n_set][n_est][nsrc][4]        estimate i against source i
+ *   all_pairs != 0: out[n_set][n_est][nsrc][nsrc][4]  estimate i against source j
+ * each { p_j, p_all, ee, status }.  SDR = 10 log10(p_j / (ee - p_j)), SIR = 10 log10(p_j / (p_all - p_j)),
+ * SAR = 10 log10(p_all / (ee - p_all)) are host arithmetic (disco_amd/metrics.py).  status[n_set] (int32) != 0, and the
+ * set's energies NaN: a pivot of the Cholesky factorisation fell to or below N 2.2e-16 times its own diagonal entry of G --
+ * a reference all zero, references linearly dependent, or G singular to working precision (mir_eval falls back to lstsq
+ * there; this does not).  Other sets of the batch are unaffected.  workspace: at least
+ * disco_bss_workspace_bytes(ctx, n_set, nsrc, flen, len): per set 8 (N0^2 + (nsrc - 1) N1^2) bytes of factors (N0, N1 = nsrc flen,
+ * flen rounded up to 32) -- 10 MB for two sources at flen 512 -- plus the correlations and their per-chunk partial sums. */
+size_t disco_bss_workspace_bytes(const disco_ctx* ctx, int64_t n_set, int nsrc, int flen, int64_t len);
+int disco_bss_eval(disco_ctx* ctx, const float* refs, const float* ests, int64_t n_set, int nsrc, int n_est, int64_t len, int start,
+                   int stop, int flen, int all_pairs, double* out, int32_t* status, void* workspace, size_t workspace_bytes,
+                   disco_stream s);
+
 /* ---- the step before the path: reverberation of dry signals ------------------------------------
  * out[i][c][0:out_len] = np.convolve(dry[i], rir[i][c])[:out_len]  (zero beyond dry_len + rir_len - 1), the operation of
  * dataset_generation/gen_disco/convolve_signals.py:160-163 (and of pyroomacoustics' room.simulate, :94-97), batched:
