@@ -48,42 +48,14 @@ extern "C" int disco_create(disco_ctx** out, const disco_cfg* cfg) {
     ctx->cfg = *cfg;
     ctx->T = 1 + cfg->length / cfg->hop;
     ctx->F = cfg->n_fft / 2 + 1;
-    ctx->d_win = nullptr;
-    ctx->d_tw = nullptr;
-    ctx->own_ws = nullptr;
-    ctx->own_ws_bytes = 0;
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    ctx->pending_chunks = 0;
-    ctx->pending_P = 0;
-    ctx->k0 = 0;
     ctx->Kl = cfg->nodes;
     ctx->zblk = cfg->nodes;
     ctx->geom_rooms = cfg->rooms;
-    ctx->half[0] = ctx->half[1] = nullptr;
-    ctx->parent = nullptr;
-    ctx->side_stream = nullptr;
-    ctx->ev_fork = ctx->ev_join = nullptr;
-    ctx->tune_runw = ctx->tune_cov_chunks = ctx->tune_step2_chunks = ctx->tune_pairs = 0;
     // per-context options (disco_set_option); the environment may preset them, and is read HERE only -- never inside a compute call
     for (int i = 0; i < DISCO_N_OPTIONS; ++i) {
         const char* e = getenv(disco_host::option_table()[i].env);
         ctx->opt[i] = e ? atoi(e) : disco_host::option_table()[i].def;
     }
-    ctx->stage_on = false;
-    ctx->scratch2 = nullptr;
-    ctx->scratch2_bytes = 0;
-    ctx->loc_chunks = 0;
-    ctx->loc_M = 0;
-    ctx->loc_X = ctx->loc_mask = nullptr;
-    ctx->pending_skiploc = 0;
-    ctx->ref_ws = nullptr;
-    ctx->ref_y = ctx->ref_s = ctx->ref_n = nullptr;
-    ctx->d_tw_conv = nullptr;
-    ctx->conv_ws = nullptr;
-    ctx->conv_ws_bytes = 0;
-    ctx->d_lens = ctx->d_lens_own = nullptr;
-    ctx->err[0] = 0;
     const int N = cfg->n_fft;
     std::vector<float> win(N);
     std::vector<c32> tw(N);
@@ -95,7 +67,6 @@ extern "C" int disco_create(disco_ctx** out, const disco_cfg* cfg) {
     }
     DevGuard dev_guard_(cfg->device);                     // the caller's current device is restored on return
     hipError_t e = dev_guard_.ok ? hipSuccess : hipErrorInvalidValue;
-    ctx->n_cu = 0;
     if (e == hipSuccess) e = hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device);
     if (ctx->n_cu < 1) ctx->n_cu = 1;
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_win, N * sizeof(float));
@@ -197,11 +168,9 @@ extern "C" void disco_destroy(disco_ctx* ctx) {
     stage_clear(ctx);
     if (ctx->d_win) (void)hipFree(ctx->d_win);
     if (ctx->d_tw) (void)hipFree(ctx->d_tw);
-    if (ctx->own_ws) (void)hipFree(ctx->own_ws);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->scratch2) (void)hipFree(ctx->scratch2);
+    for (DevBlock* b : {&ctx->own_ws, &ctx->partials.full, &ctx->partials.tail, &ctx->conv_ws})
+        if (b->p) (void)hipFree(b->p);
     if (ctx->d_tw_conv && ctx->d_tw_conv != ctx->d_tw) (void)hipFree(ctx->d_tw_conv);
-    if (ctx->conv_ws) (void)hipFree(ctx->conv_ws);
     if (ctx->d_lens_own) (void)hipFree(ctx->d_lens_own);
     delete ctx;
 }
@@ -214,7 +183,7 @@ extern "C" int disco_set_node_shard(disco_ctx* ctx, int first_node, int node_cou
         return fail(ctx, DISCO_E_UNSUPPORTED, "disco_set_node_shard: per-room lengths are set (disco_set_lengths); a node shard does not take them");
     ctx->k0 = first_node;
     ctx->Kl = node_count;
-    ctx->pending_chunks = 0;
+    pending_drop(ctx);
     return 0;
 }
 
@@ -225,9 +194,7 @@ extern "C" int disco_set_lengths(disco_ctx* ctx, const int32_t* lengths, int n_r
     const disco_cfg& c = ctx->cfg;
     if (ctx->parent) return fail(ctx, DISCO_E_ARG, "disco_set_lengths: a half-batch child follows its parent");
     auto drop_state = [](disco_ctx* x) {                   // partial sums / reference state of other lengths must not be re-used
-        x->pending_chunks = 0;
-        x->pending_skiploc = 0;
-        x->loc_M = 0;
+        partials_forget(x);
         x->ref_ws = nullptr;
     };
     if (!lengths) {
@@ -326,8 +293,7 @@ extern "C" int disco_set_tuning(disco_ctx* ctx, int stft_frames_per_wave, int co
     ctx->tune_cov_chunks = cov_chunks;
     ctx->tune_step2_chunks = step2_chunks;
     ctx->tune_pairs = istft_pairs;
-    ctx->pending_chunks = 0;           // partial sums of another geometry must not be re-used
-    ctx->loc_M = 0;
+    partials_forget(ctx);              // partial sums of another geometry must not be re-used
     for (int h = 0; h < 2; ++h)
         if (ctx->half[h]) {
             const int rc = disco_set_tuning(ctx->half[h], stft_frames_per_wave, cov_chunks, step2_chunks, istft_pairs);

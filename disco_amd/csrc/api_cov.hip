@@ -26,58 +26,38 @@ int cov1_f64_chunks(const disco_ctx* ctx) {
     return (int)std::max<long long>(1, std::min<long long>(std::min(8, ctx->T), (8LL * ctx->n_cu + wgs - 1) / wgs));
 }
 
-// A block that has to GROW is freed and allocated anew: whatever the context remembered about partial sums sitting in it (step-1 sums a
-// later step 2 would pair with, sums a pending solve would read) is forgotten with it -- a staged-API caller who changes an option or the
-// tuning between a covariance call and its solve gets "no covariance call has left partial sums", not a solve of uninitialised memory.
-static void forget_partials(disco_ctx* ctx) {
-    ctx->loc_M = 0;
-    ctx->loc_X = nullptr;
-    ctx->loc_mask = nullptr;
-    ctx->pending_chunks = 0;
-    ctx->pending_skiploc = 0;
-}
-
-int ensure_scratch(disco_ctx* ctx, size_t bytes) {
-    if (ctx->scratch_bytes >= bytes) return 0;
-    forget_partials(ctx);
-    if (ctx->scratch) {
-        HIPCHK(ctx, hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->scratch, bytes));
-    ctx->scratch_bytes = bytes;
-    return 0;
-}
-
-int ensure_scratch2(disco_ctx* ctx, size_t bytes) {
-    if (ctx->scratch2_bytes >= bytes) return 0;
-    if (ctx->pending_skiploc) {
-        // a pending step-2 solve reads this block: it is forgotten.  The step-1 sums (loc_M / loc_X / loc_mask) sit in `scratch`, which
-        // is untouched here -- the callers have already decided "skiploc" from them and go on to merge that leading block (round-5 ADVICE).
-        ctx->pending_chunks = 0;
-        ctx->pending_skiploc = 0;
-    }
-    if (ctx->scratch2) {
-        HIPCHK(ctx, hipFree(ctx->scratch2));
-        ctx->scratch2 = nullptr;
-        ctx->scratch2_bytes = 0;
-    }
-    HIPCHK(ctx, hipMalloc(&ctx->scratch2, bytes));
-    ctx->scratch2_bytes = bytes;
-    return 0;
-}
-
-int cov_finalize(disco_ctx* ctx, int chunks, int P, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
+int cov_finalize(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
+    PendingSums ps;
+    if (!partials_pending(ctx, &ps) || ps.part_loc) return fail(ctx, DISCO_E_ARG, "cov_finalize: no whole-triangle partial sums are pending");
     const long long n_gf = (long long)ctx->cfg.rooms * ctx->Kl * ctx->F;
     hipLaunchKernelGGL(k_cov_finalize, dim3((unsigned)std::min<long long>((n_gf + 127) / 128, 65535)), dim3(128), 0,
-                       (hipStream_t)s, (const float4*)ctx->scratch, (c32*)Rss, (c32*)Rnn, n_gf, ctx->F, chunks, P,
+                       (hipStream_t)s, ps.part, (c32*)Rss, (c32*)Rnn, n_gf, ctx->F, ps.blocks, ps.P,
                        1.0f / (float)ctx->T, ctx->d_lens, ctx->Kl);
     return check_launch(ctx, "k_cov_finalize");
 }
-// 17 <= P <= 32 (k_cov_wide.h): always the full triangle into `scratch` (the step-1 sums are not re-used: no skiploc)
+static CovArgs cov_args(const disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn, float4* part,
+                        int chunks, int mask_remote) {
+    CovArgs a;
+    a.X = (const c32*)X;
+    a.mask = mask;
+    a.Zs = (const c32*)Zs;
+    a.Zn = (const c32*)Zn;
+    a.part = part;
+    a.K = ctx->cfg.nodes;
+    a.T = ctx->T;
+    a.F = ctx->F;
+    a.chunks = chunks;
+    a.mask_remote = mask_remote;
+    a.Kl = ctx->Kl;
+    a.k0 = ctx->k0;
+    a.zblk = ctx->zblk;
+    a.R = ctx->cfg.rooms;
+    return a;
+}
+
+// 17 <= P <= 32 (k_cov_wide.h): always the whole triangle into the full block (the step-1 sums are not re-used: no skiploc)
 static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn,
-                             int mask_remote, int P, int* chunks_out, disco_stream s) {
+                             int mask_remote, int P, disco_stream s) {
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics, KR = P - M;
     const int chunks = cov_chunks(ctx);
@@ -87,45 +67,23 @@ static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* ma
     const long long n_items = G * (tiles + 1) * chunks * nbg;
     const long long grid = (n_items + DISCO_COV_WIDE_XCD - 1) / DISCO_COV_WIDE_XCD * DISCO_COV_WIDE_XCD;
     if (grid > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: batch too large (P > 16: more than 2^31 workgroups)");
-    // the scratch this batch needs, G x chunks x F x NP x 16 B, checked before anything runs
+    // the block this batch needs, G x chunks x F x NP x 16 B, checked before anything runs
     const size_t need = (size_t)G * chunks * ctx->F * NP * sizeof(float4);
-    if (ctx->scratch_bytes < need) {
-        int rc = ensure_scratch(ctx, need);
-        if (rc) {
-            (void)hipGetLastError();
-            char m[400];
-            snprintf(m, sizeof(m), "disco_cov_masked: P = %d needs %.2f GiB of partial-sum scratch (%lld units x %d chunks x %d bins x %d pairs "
-                     "x 16 B), which the device cannot provide: split the batch into fewer rooms", P, need / 1073741824.0, G, chunks, ctx->F, NP);
-            return fail(ctx, DISCO_E_UNSUPPORTED, m);
-        }
+    int rc = 0;
+    float4* part = partials_begin(ctx, need, false, &rc);
+    if (rc) {
+        (void)hipGetLastError();
+        char m[400];
+        snprintf(m, sizeof(m), "disco_cov_masked: P = %d needs %.2f GiB of partial-sum scratch (%lld units x %d chunks x %d bins x %d pairs "
+                 "x 16 B), which the device cannot provide: split the batch into fewer rooms", P, need / 1073741824.0, G, chunks, ctx->F, NP);
+        return fail(ctx, DISCO_E_UNSUPPORTED, m);
     }
-    CovArgs a;
-    a.X = (const c32*)X;
-    a.mask = mask;
-    a.Zs = (const c32*)Zs;
-    a.Zn = (const c32*)Zn;
-    a.part = (float4*)ctx->scratch;
-    a.K = c.nodes;
-    a.T = ctx->T;
-    a.F = ctx->F;
-    a.chunks = chunks;
-    a.mask_remote = mask_remote;
-    a.Kl = ctx->Kl;
-    a.k0 = ctx->k0;
-    a.zblk = ctx->zblk;
-    a.R = c.rooms;
+    const CovArgs a = cov_args(ctx, X, mask, Zs, Zn, part, chunks, mask_remote);
     if (Zs == Zn)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<true>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<false>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
-    *chunks_out = chunks;
-    ctx->pending_chunks = chunks;
-    ctx->pending_P = P;
-    ctx->pending_skiploc = 0;
-    ctx->loc_M = 0;                              // `scratch` no longer holds step-1 sums
-    ctx->loc_chunks = chunks;
-    ctx->loc_X = X;
-    ctx->loc_mask = mask;
+    partials_commit(ctx, chunks, P, false);
     return check_launch(ctx, "k_cov_wide");
 }
 
@@ -133,11 +91,11 @@ static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* ma
 bool cov_split_shape(int M, int KR);
 bool launch_cov_split_shape(int M, int KR, bool skiploc, int sub, unsigned nblk, hipStream_t st, const disco::CovArgs& a);
 
-// skiploc (step 2 only, internal): the caller guarantees that `scratch` holds the step-1 partial sums of THIS X with THIS
-// mask (ctx->loc_M == M): the leading M x M block is then neither accumulated nor written, the partial sums go to `scratch2`
-// and the solver assembles the pencil from both.  Honoured only by k_cov_split; the return value of *skiploc_used says so.
+// skiploc (step 2 only, internal): where the step-1 partial sums of THIS X with THIS mask are still kept (step1_held), the leading
+// M x M block is neither accumulated nor written, the partial sums go to the tail block and the solver assembles the pencil from
+// both.  Honoured only by k_cov_split.
 int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn,
-                 int mask_remote, int P, int* chunks_out, disco_stream s, bool skiploc) {
+                 int mask_remote, int P, disco_stream s, bool skiploc) {
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics, KR = P - M;
     if (!X || !mask) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: null argument");
@@ -145,7 +103,7 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
     if (KR > 0 && (!Zs || !Zn)) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: Zs/Zn required when P > M");
     if (M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: M > 8 mics per node not supported");
     if (P > CW_PMAX) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: P = M + K - 1 > 32 not supported");
-    if (P > CB_PMAX) return cov_partials_wide(ctx, X, mask, Zs, Zn, mask_remote, P, chunks_out, s);
+    if (P > CB_PMAX) return cov_partials_wide(ctx, X, mask, Zs, Zn, mask_remote, P, s);
     int chunks = cov_chunks(ctx);
     const long long G = (long long)c.rooms * ctx->Kl;
     const int NP = P * (P + 1) / 2;
@@ -156,25 +114,11 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
     if (sub == 64) chunks = cov1_f64_chunks(ctx);
     const int blocks = sub == 64 ? 2 * chunks : chunks;
     const size_t need = (size_t)G * blocks * ctx->F * NP * sizeof(float4);
-    skiploc = skiploc && split && KR > 0 && ctx->loc_M == M && ctx->loc_X == X && ctx->loc_mask == mask;
+    skiploc = skiploc && split && KR > 0 && step1_held(ctx, X, mask);
     int rc = 0;
-    rc = skiploc ? ensure_scratch2(ctx, need) : ensure_scratch(ctx, need);
+    float4* part = partials_begin(ctx, need, skiploc, &rc);
     if (rc) return rc;
-    CovArgs a;
-    a.X = (const c32*)X;
-    a.mask = mask;
-    a.Zs = (const c32*)Zs;
-    a.Zn = (const c32*)Zn;
-    a.part = (float4*)(skiploc ? ctx->scratch2 : ctx->scratch);
-    a.K = c.nodes;
-    a.T = ctx->T;
-    a.F = ctx->F;
-    a.chunks = chunks;
-    a.mask_remote = mask_remote;
-    a.Kl = ctx->Kl;
-    a.k0 = ctx->k0;
-    a.zblk = ctx->zblk;
-    a.R = c.rooms;
+    const CovArgs a = cov_args(ctx, X, mask, Zs, Zn, part, chunks, mask_remote);
     const dim3 grid((unsigned)(G * chunks)), block((unsigned)(ctx->F - 1 + 64));
     bool launched = false;
     if (split) {                // 9 <= P <= 16, one vector for both statistics: one block of pairs per wave
@@ -209,18 +153,9 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_big<false>), dim3((unsigned)nblk), dim3(64 * CB_S), 0, (hipStream_t)s, a, M, KR);
     }
-    *chunks_out = blocks;
-    ctx->pending_chunks = blocks;
-    ctx->pending_P = P;
-    ctx->pending_skiploc = skiploc ? 1 : 0;
-    if (!skiploc) {
-        // `scratch` now holds THIS call's partial sums: step-1 ones (P == M, all nodes here) can be re-used by a step 2
-        // on the same mask, anything else invalidates what k_stft_cov / an earlier step-1 call left
-        ctx->loc_M = (KR == 0 && !sharded(ctx)) ? M : 0;
-        ctx->loc_chunks = blocks;
-        ctx->loc_X = X;
-        ctx->loc_mask = mask;
-    }
+    partials_commit(ctx, blocks, P, skiploc);
+    // step-1 sums (P == M, all nodes here) can be re-used by a step 2 on the same mask
+    if (KR == 0 && !sharded(ctx)) step1_keep(ctx, X, mask);
     return check_launch(ctx, "k_cov");
 }
 }  // namespace disco_host
@@ -230,8 +165,7 @@ extern "C" int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float*
                                 disco_stream s) {
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: Rss and Rnn must both be given or both be NULL");
-    int chunks = 1;
-    int rc = cov_partials(ctx, X, mask, Zs, Zn, mask_remote, P, &chunks, s);
+    int rc = cov_partials(ctx, X, mask, Zs, Zn, mask_remote, P, s);
     if (rc || !Rss) return rc;
-    return cov_finalize(ctx, chunks, P, Rss, Rnn, s);
+    return cov_finalize(ctx, Rss, Rnn, s);
 }

@@ -191,15 +191,10 @@ extern "C" int disco_rir_convolve(disco_ctx* ctx, const float* dry, const float*
     const size_t x_bytes = (size_t)n_sig * nb * CV_F * sizeof(c32);
     const size_t h_bytes = (size_t)n_sig * n_ch * P * CV_F * sizeof(c32);
     const size_t need = align_up(x_bytes) + h_bytes;
-    if (ctx->conv_ws_bytes < need) {
-        if (ctx->conv_ws) HIPCHK(ctx, hipFree(ctx->conv_ws));
-        ctx->conv_ws = nullptr;
-        ctx->conv_ws_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->conv_ws, need));
-        ctx->conv_ws_bytes = need;
-    }
-    c32* X = (c32*)ctx->conv_ws;
-    c32* H = (c32*)((char*)ctx->conv_ws + align_up(x_bytes));
+    const int rcw = grow(ctx, ctx->conv_ws, need);
+    if (rcw) return rcw;
+    c32* X = (c32*)ctx->conv_ws.p;
+    c32* H = (c32*)((char*)ctx->conv_ws.p + align_up(x_bytes));
     const long long nx = (long long)n_sig * nb, nh = (long long)n_sig * n_ch * P;
     auto grid_of = [](long long items) { return dim3((unsigned)std::min<long long>((items + CV_WAVES - 1) / CV_WAVES, 1 << 20)); };
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_spectra<true>), grid_of(nx), dim3(64 * CV_WAVES), 0, st, dry, (long long)dry_len, nb, nx, X,

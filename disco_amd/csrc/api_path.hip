@@ -120,16 +120,9 @@ int acquire_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, const Ws
             return fail(ctx, DISCO_E_ARG, m.c_str());
         }
     } else {
-        if (ctx->own_ws_bytes < l.total) {
-            if (ctx->own_ws) {
-                HIPCHK(ctx, hipFree(ctx->own_ws));
-                ctx->own_ws = nullptr;
-                ctx->own_ws_bytes = 0;
-            }
-            HIPCHK(ctx, hipMalloc(&ctx->own_ws, l.total));
-            ctx->own_ws_bytes = l.total;
-        }
-        ws = (char*)ctx->own_ws;
+        const int rc = ensure_own_ws(ctx, l.total);
+        if (rc) return rc;
+        ws = (char*)ctx->own_ws.p;
     }
     if (ctx->ref_ws == ws) ctx->ref_ws = nullptr;      // a steps = 1 state of disco_tango_reference in this workspace is overwritten
     *ws_out = ws;
@@ -142,17 +135,15 @@ int reserve_scratch(disco_ctx* ctx) {
     const size_t G = (size_t)c.rooms * ctx->Kl;
     const int P2 = c.mics + c.nodes - 1;
     if (P2 > CB_PMAX && P2 <= CW_PMAX && c.mics <= 8) {
-        // 17 <= P <= 32: step 1 (P = M, the chunk counts below) and step 2 (k_cov_wide, cov_chunks) size `scratch`; `scratch2` only
-        // ever holds re-used step-1 sums, which the wide route does not take
+        // 17 <= P <= 32: step 1 (P = M, the chunk counts below) and step 2 (k_cov_wide, cov_chunks) size the full block; the tail block
+        // only ever pairs with re-used step-1 sums, which the wide route does not take
         const size_t NP1 = (size_t)c.mics * (c.mics + 1) / 2, NP2 = (size_t)P2 * (P2 + 1) / 2;
         int ch1 = cov_chunks(ctx);
         if (c.mics >= 7) ch1 = std::max(ch1, 2 * cov1_f64_chunks(ctx));
         ch1 = std::max(ch1, stft_cov_chunks(ctx, nullptr));
         const size_t need1 = G * (size_t)ch1 * ctx->F * NP1 * sizeof(float4);
         const size_t need2 = G * (size_t)cov_chunks(ctx) * ctx->F * NP2 * sizeof(float4);
-        int rc = ensure_scratch(ctx, std::max(need1, need2));
-        if (!rc) rc = ensure_scratch2(ctx, need1);
-        return rc;
+        return partials_reserve(ctx, std::max(need1, need2), need1);
     }
     const size_t P = (size_t)std::min(P2, 16);
     const size_t NP = P * (P + 1) / 2;
@@ -161,11 +152,56 @@ int reserve_scratch(disco_ctx* ctx) {
     if (c.mics <= 8) chunks = std::max(chunks, stft_cov_chunks(ctx, nullptr));
     if (c.mics + c.nodes - 1 > 8) chunks = std::max(chunks, room_chunks(ctx));
     const size_t need = G * (size_t)chunks * ctx->F * NP * sizeof(float4);
-    int rc = ensure_scratch(ctx, need);
-    if (!rc) rc = ensure_scratch2(ctx, need);
-    return rc;
+    return partials_reserve(ctx, need, need);
 }
 }  // namespace disco_host
+
+// step 2 on the on-chip z exchange: whenever all nodes of a room share the GPU and P <= 8, unless the context asks for the staged form
+static bool fused_route(const disco_ctx* ctx) {
+    const disco_cfg& c = ctx->cfg;
+    return c.nodes > 1 && c.mics + c.nodes - 1 <= 8 && !(c.flags & DISCO_FLAG_STAGED_STEP2);
+}
+
+// exchange + step-2 statistics with z materialised, mask_for_z = 'local': ONE pass over X for every node of a room where the shape and the
+// context's state allow it (k_room_cov), else the filter pass followed by the covariance pass that reads X again and the K - 1 remote z's
+static void push_staged_step2(disco_ctx* ctx, Steps& st, const disco_c32* X, const float* mask_w, bool same_mask, const disco_c32* w_loc,
+                              disco_c32* z, bool store_z) {
+    st.push_back({nullptr, false, [=](disco_stream s) {
+        const disco_cfg& c = ctx->cfg;
+        if (same_mask && room_cov_ok(ctx, X, mask_w)) return STAGE(ctx, s, "room_cov2", room_cov_partials(ctx, X, mask_w, w_loc, z, s, store_z));
+        const int rc = STAGE(ctx, s, "apply1", disco_apply(ctx, X, nullptr, w_loc, c.mics, 1, z, s));
+        if (rc) return rc;
+        const disco_c32* zr = c.nodes > 1 ? z : nullptr;
+        return STAGE(ctx, s, "cov2", cov_partials(ctx, X, mask_w, zr, zr, 1, c.mics + c.nodes - 1, s, same_mask && c.nodes > 1));
+    }});
+}
+
+// the global filter + iSTFT: wide shapes in one pass, yf stays on chip (and goes out only when the caller asked for it: yf may be NULL)
+static void push_apply2_istft(disco_ctx* ctx, Steps& st, const disco_c32* X, const disco_c32* z, const disco_c32* w, disco_c32* yf,
+                              disco_c32* yo, float* out) {
+    const disco_cfg& c = ctx->cfg;
+    const int64_t G = (int64_t)c.rooms * c.nodes;
+    const int P2 = c.mics + c.nodes - 1;
+    if (c.nodes > 1 && apply_istft_wide_ok(ctx)) {
+        st.push_back({"apply2_istft", false, [=](disco_stream s) { return apply_istft_wide(ctx, X, z, w, yf, out, s); }});
+        return;
+    }
+    st.push_back({"apply2", false, [=](disco_stream s) { return disco_apply(ctx, X, c.nodes > 1 ? z : nullptr, w, P2, 1, yo, s); }});
+    st.push_back({"istft", false, [=](disco_stream s) { return disco_istft(ctx, yo, G, out, s); }});
+}
+
+// a whole-path call: one list of steps on the caller's stream, or -- `overlap` and the half-batch children exist -- one list per child
+static int run_path(disco_ctx* ctx, const PathArgs& a, bool overlap, const std::function<void(disco_ctx*, const PathArgs&, Steps&)>& build,
+                    disco_stream s) {
+    if (overlap && overlap_applies(ctx) && ctx->half[0] && ctx->half[1]) {
+        Steps st[2];
+        for (int h = 0; h < 2; ++h) build(ctx->half[h], child_args(ctx, a, h), st[h]);
+        return run_pipelined(ctx, st, s);
+    }
+    Steps st;
+    build(ctx, a, st);
+    return run_steps(ctx, st, s);
+}
 
 // offline_tango's y branch as a list of steps (tango.py:326-450 + 528); `a` names this context's slice of the batch
 static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
@@ -180,34 +216,31 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
     disco_c32* w = (disco_c32*)(a.ws + l.w);
     disco_c32* w2 = (disco_c32*)(a.ws + l.w2);
     const int64_t G = (int64_t)c.rooms * c.nodes;
-    const int M = c.mics, P2 = c.mics + c.nodes - 1;
+    const int M = c.mics;
     const bool same_mask = mask_w == mask_z;
     auto solve_pending = [ctx](disco_c32* w_out) { return [ctx, w_out](disco_stream s) { return disco_gevd_mwf_r1_pending(ctx, ctx->cfg.mu, w_out, nullptr, s); }; };
 
     if (c.nodes == 1 && same_mask && !z_y && !yf && c.n_fft == 512 && M <= 4) {
         // single node, enhanced output only (config C2): nothing is materialised -- one pass over the samples for the
         // statistics, one for filter + iSTFT with the spectra recomputed (get_z_signals.py:274-315 + tango.py:528)
-        st.push_back({nullptr, false, [=](disco_stream s) { int ch = 1; return stft_cov_partials(ctx, y, mask_z, nullptr, &ch, s, false); }});
+        st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, nullptr, s, false); }});
         st.push_back({"solve1", true, solve_pending(w)});
         st.push_back({"stft_apply_istft", false, [=](disco_stream s) { return stft_apply_istft(ctx, y, w, out, s); }});
         return;
     }
     // step 1 (tango.py:326-376): STFT + covariance in one pass, solve straight from the partial sums
-    const bool fused_route = c.nodes > 1 && P2 <= 8 && !(c.flags & DISCO_FLAG_STAGED_STEP2);
     // per-room lengths: both readers of X on the fused route without yf (k_step2_cov_fused, k_step2_apply_istft) stop at a room's own
     // frames, so the frames of X beyond them need not be written; every other route reads them and finds the zeros it relies on
-    const bool x_zeros = !(fused_route && !yf && c.n_fft == 512 && step2_apply_istft_ok(ctx));
-    st.push_back({nullptr, false, [=](disco_stream s) { int ch = 1; return stft_cov_partials(ctx, y, mask_z, X, &ch, s, true, x_zeros); }});
+    const bool x_zeros = !(fused_route(ctx) && !yf && c.n_fft == 512 && step2_apply_istft_ok(ctx));
+    st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, X, s, true, x_zeros); }});
     st.push_back({"solve1", true, solve_pending(w)});
 
-    if (fused_route) {
-        // step 2 on the on-chip z exchange (default whenever all nodes of a room share the GPU and P <= 8)
+    if (fused_route(ctx)) {
         // same mask array in both steps (oracle masks; a DNN mask re-used, tango.py:388-389): the leading M x M block of the
         // step-2 covariances IS the step-1 covariance still held as partial sums -> not recomputed
         st.push_back({"step2_cov", false, [=](disco_stream s) {
-            int ch = 1;
-            if (same_mask && ctx->loc_M == M) return disco_step2_cov_fused_reuse(ctx, X, mask_w, w, z_y, s);
-            return step2_cov_partials(ctx, X, mask_w, w, z_y, &ch, s);
+            if (step1_held(ctx, X, mask_w)) return disco_step2_cov_fused_reuse(ctx, X, mask_w, w, z_y, s);
+            return step2_cov_partials(ctx, X, mask_w, w, z_y, s);
         }});
         st.push_back({"solve2", true, solve_pending(w2)});
         if (!yf && c.n_fft == 512) {   // yf not asked for: filter + iSTFT in one pass, yf stays on chip (shapes the kernel takes)
@@ -235,22 +268,10 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
         }});
         return;
     }
-    // exchange + step 2 (tango.py:378-450) with z materialised, mask_for_z = 'local': wide shapes take z + the step-2 statistics of a
-    // whole room in one pass (k_room_cov) when the context's state allows it, else the filter pass + the covariance pass
-    st.push_back({nullptr, false, [=](disco_stream s) {
-        int ch = 1, rc;
-        if (c.nodes > 1 && same_mask && room_cov_ok(ctx, X, mask_w))
-            return STAGE(ctx, s, "room_cov2", room_cov_partials(ctx, X, mask_w, w, z, &ch, s));
-        if ((rc = STAGE(ctx, s, "apply1", disco_apply(ctx, X, nullptr, w, M, 1, z, s)))) return rc;
-        return STAGE(ctx, s, "cov2", cov_partials(ctx, X, mask_w, c.nodes > 1 ? z : nullptr, c.nodes > 1 ? z : nullptr, 1, P2, &ch, s, same_mask && c.nodes > 1));
-    }});
+    // exchange + step 2 (tango.py:378-450) with z materialised
+    push_staged_step2(ctx, st, X, mask_w, same_mask, w, z, true);
     st.push_back({"solve2", true, solve_pending(w)});
-    if (c.nodes > 1 && apply_istft_wide_ok(ctx)) {      // wide shapes: yf stays on chip (and goes out only when the caller asked for it)
-        st.push_back({"apply2_istft", false, [=](disco_stream s) { return apply_istft_wide(ctx, X, z, w, yf, out, s); }});
-        return;
-    }
-    st.push_back({"apply2", false, [=](disco_stream s) { return disco_apply(ctx, X, c.nodes > 1 ? z : nullptr, w, P2, 1, yo, s); }});
-    st.push_back({"istft", false, [=](disco_stream s) { return disco_istft(ctx, yo, G, out, s); }});
+    push_apply2_istft(ctx, st, X, z, w, yf, yo, out);
 }
 
 extern "C" int disco_tango_enhance(disco_ctx* ctx, const float* y, const float* mask_z, const float* mask_w, float* out,
@@ -263,17 +284,8 @@ extern "C" int disco_tango_enhance(disco_ctx* ctx, const float* y, const float* 
     int rcw = acquire_ws(ctx, workspace, workspace_bytes, l, &ws, "disco_tango_enhance");
     if (rcw) return rcw;
     const PathArgs a{y, mask_z, mask_w, out, z_y, yf, ws};
-    const disco_cfg& c0 = ctx->cfg;
-    const bool fused_route = c0.nodes > 1 && c0.mics + c0.nodes - 1 <= 8 && !(c0.flags & DISCO_FLAG_STAGED_STEP2);
     // by default only where it was measured to pay: the fused route (C3: 19.67 -> 19.14 ms); forced (2 / 3) for every route
-    if (overlap_applies(ctx) && ctx->half[0] && ctx->half[1] && (fused_route || ctx->opt[DISCO_OPT_OVERLAP_SOLVES] >= 2)) {
-        Steps st[2];
-        for (int h = 0; h < 2; ++h) enhance_steps(ctx->half[h], child_args(ctx, a, h), st[h]);
-        return run_pipelined(ctx, st, s);
-    }
-    Steps st;
-    enhance_steps(ctx, a, st);
-    return run_steps(ctx, st, s);
+    return run_path(ctx, a, fused_route(ctx) || ctx->opt[DISCO_OPT_OVERLAP_SOLVES] >= 2, enhance_steps, s);
 }
 
 // ---- reference outputs: all nine returns of offline_tango, device resident ------------------------------------------------
@@ -311,8 +323,7 @@ extern "C" size_t disco_reference_workspace_bytes(const disco_ctx* ctx) { return
 
 extern "C" size_t disco_owned_bytes(const disco_ctx* ctx) {
     if (!ctx) return 0;
-    return ctx->scratch_bytes + ctx->scratch2_bytes + ctx->own_ws_bytes + ctx->conv_ws_bytes + disco_owned_bytes(ctx->half[0]) +
-           disco_owned_bytes(ctx->half[1]);
+    return partials_bytes(ctx) + ctx->own_ws.bytes + ctx->conv_ws.bytes + disco_owned_bytes(ctx->half[0]) + disco_owned_bytes(ctx->half[1]);
 }
 
 extern "C" int disco_reserve(disco_ctx* ctx, int own_workspace) {
@@ -324,17 +335,7 @@ extern "C" int disco_reserve(disco_ctx* ctx, int own_workspace) {
     if (rc || !own_workspace) return rc;
     size_t need = ws_layout(ctx).total;
     if (own_workspace == 2) need = std::max(need, ref_layout(ctx).total);
-    if (ctx->own_ws_bytes < need) {
-        if (ctx->own_ws) {
-            if (ctx->ref_ws == ctx->own_ws) ctx->ref_ws = nullptr;
-            HIPCHK(ctx, hipFree(ctx->own_ws));
-            ctx->own_ws = nullptr;
-            ctx->own_ws_bytes = 0;
-        }
-        HIPCHK(ctx, hipMalloc(&ctx->own_ws, need));
-        ctx->own_ws_bytes = need;
-    }
-    return 0;
+    return ensure_own_ws(ctx, need);
 }
 
 extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float* s_img, const float* n_img, const float* mask_z_in,
@@ -355,17 +356,11 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
     if (ws) {
         if (workspace_bytes < l.total) return fail(ctx, DISCO_E_ARG, "disco_tango_reference: workspace too small");
     } else {
-        if (ctx->own_ws_bytes < l.total) {
-            if (steps == 2) return fail(ctx, DISCO_E_ARG, "disco_tango_reference: steps = 2 needs the workspace of the preceding steps = 1 call");
-            if (ctx->own_ws) {
-                HIPCHK(ctx, hipFree(ctx->own_ws));
-                ctx->own_ws = nullptr;
-                ctx->own_ws_bytes = 0;
-            }
-            HIPCHK(ctx, hipMalloc(&ctx->own_ws, l.total));
-            ctx->own_ws_bytes = l.total;
-        }
-        ws = (char*)ctx->own_ws;
+        if (ctx->own_ws.bytes < l.total && steps == 2)
+            return fail(ctx, DISCO_E_ARG, "disco_tango_reference: steps = 2 needs the workspace of the preceding steps = 1 call");
+        const int rcw = ensure_own_ws(ctx, l.total);
+        if (rcw) return rcw;
+        ws = (char*)ctx->own_ws.p;
     }
     if (steps == 2 && !(ctx->ref_ws == ws && ctx->ref_y == y && ctx->ref_s == s_img && ctx->ref_n == n_img))
         return fail(ctx, DISCO_E_ARG, "disco_tango_reference: steps = 2 needs the state a steps = 1 call with the same y, s, n left in the same "
@@ -408,8 +403,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
             if ((rc = disco_cov_masked(ctx, Xn, mc, nullptr, nullptr, 0, M, Rtmp, Rnn, s))) return rc;      // mask 0: Rnn = <N N^H>  (Rtmp = 0)
             if ((rc = disco_gevd_mwf_r1(ctx, Rss, Rnn, G * ctx->F, M, c.mu, w_loc, nullptr, s))) return rc;
         } else {
-            int chunks = 1;
-            if ((rc = cov_partials(ctx, Xy, mz, nullptr, nullptr, 0, M, &chunks, s))) return rc;
+            if ((rc = cov_partials(ctx, Xy, mz, nullptr, nullptr, 0, M, s))) return rc;
             if ((rc = disco_gevd_mwf_r1_pending(ctx, c.mu, w_loc, nullptr, s))) return rc;
         }
         if ((rc = disco_apply(ctx, Xy, nullptr, w_loc, M, 1, zy, s))) return rc;
@@ -466,8 +460,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
         }
         if ((rc = check_launch(ctx, "reference rows"))) return rc;
     }
-    int chunks2 = 1;
-    if ((rc = cov_partials(ctx, Xy, mw, K > 1 ? Zs_rows : nullptr, K > 1 ? Zn_rows : nullptr, mask_remote, P2, &chunks2, s))) return rc;
+    if ((rc = cov_partials(ctx, Xy, mw, K > 1 ? Zs_rows : nullptr, K > 1 ? Zn_rows : nullptr, mask_remote, P2, s))) return rc;
     if ((rc = disco_gevd_mwf_r1_pending(ctx, c.mu, w_glo, nullptr, s))) return rc;
     // ---- the global filter on the mixture and on both images (tango.py:445-450); outputs straight into the caller's arrays
     if (out->yf && (rc = disco_apply(ctx, Xy, K > 1 ? zy : nullptr, w_glo, P2, 1, out->yf, s))) return rc;
@@ -490,22 +483,13 @@ static void iterated_steps(disco_ctx* ctx, const PathArgs& a, int iters, Steps& 
     const int64_t G = (int64_t)c.rooms * c.nodes;
     const int M = c.mics, P2 = c.mics + c.nodes - 1;
     const bool same_mask = mask_w == mask_z;
-    st.push_back({nullptr, false, [=](disco_stream s) { int ch = 1; return stft_cov_partials(ctx, y, mask_z, X, &ch, s); }});
+    st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, X, s); }});
     st.push_back({"solve1", true, [=](disco_stream s) { return disco_gevd_mwf_r1_pending(ctx, c.mu, w_loc, nullptr, s); }});
     for (int it = 0; it < iters; ++it) {
         // compression with the current w_loc (step 1's, then the local part of the previous iteration's filter) and the step-2
-        // statistics: ONE pass over X for every node of a room where the shape allows it (k_room_cov), else the filter pass
-        // followed by the covariance pass that reads X again and the K - 1 remote z's
-        const bool last_pass = it + 1 == iters;          // only the last pass's z is read again (by the filter pass; it is what z_y returns)
-        st.push_back({nullptr, false, [=](disco_stream s) {
-            int ch = 1, rc;
-            if (same_mask && room_cov_ok(ctx, X, mask_w))
-                return STAGE(ctx, s, "room_cov2", room_cov_partials(ctx, X, mask_w, w_loc, z, &ch, s, last_pass));
-            if ((rc = STAGE(ctx, s, "apply1", disco_apply(ctx, X, nullptr, w_loc, M, 1, z, s)))) return rc;
-            return STAGE(ctx, s, "cov2", cov_partials(ctx, X, mask_w, c.nodes > 1 ? z : nullptr, c.nodes > 1 ? z : nullptr, 1, P2, &ch, s,
-                                                      same_mask && c.nodes > 1));
-        }});
+        // statistics; only the last pass's z is read again (by the filter pass; it is what z_y returns)
         const bool last = it + 1 == iters;
+        push_staged_step2(ctx, st, X, mask_w, same_mask, w_loc, z, last);
         st.push_back({"solve2", true, [=](disco_stream s) {
             int rc = disco_gevd_mwf_r1_pending(ctx, c.mu, w_glo, nullptr, s);
             if (rc || last) return rc;
@@ -516,12 +500,7 @@ static void iterated_steps(disco_ctx* ctx, const PathArgs& a, int iters, Steps& 
             return check_launch(ctx, "k_filter_head");
         }});
     }
-    if (c.nodes > 1 && apply_istft_wide_ok(ctx)) {
-        st.push_back({"apply2_istft", false, [=](disco_stream s) { return apply_istft_wide(ctx, X, z, w_glo, a.yf, out, s); }});
-        return;
-    }
-    st.push_back({"apply2", false, [=](disco_stream s) { return disco_apply(ctx, X, c.nodes > 1 ? z : nullptr, w_glo, P2, 1, yo, s); }});
-    st.push_back({"istft", false, [=](disco_stream s) { return disco_istft(ctx, yo, G, out, s); }});
+    push_apply2_istft(ctx, st, X, z, w_glo, a.yf, yo, out);
 }
 
 extern "C" int disco_tango_enhance_iterated(disco_ctx* ctx, const float* y, const float* mask_z, const float* mask_w, int iters,
@@ -538,12 +517,5 @@ extern "C" int disco_tango_enhance_iterated(disco_ctx* ctx, const float* y, cons
     // The overlapped form on the wide shapes: with the LDS group solver it lost (C5: 46.4 ms plain, 48.0 / 48.4 ms overlapped -- the room
     // pass takes a whole CU per workgroup and the solver's LDS blocks compete with it); with the register / DPP solver (k_solve_dpp.h:
     // 15 KB of LDS per wave, float64 VALU only) it pays: 38.40 -> 37.88 ms (profiles/r03_o_C5_overlap*.json).  Default like the fused route.
-    if (overlap_applies(ctx) && ctx->half[0] && ctx->half[1]) {
-        Steps st[2];
-        for (int h = 0; h < 2; ++h) iterated_steps(ctx->half[h], child_args(ctx, a, h), iters, st[h]);
-        return run_pipelined(ctx, st, s);
-    }
-    Steps st;
-    iterated_steps(ctx, a, iters, st);
-    return run_steps(ctx, st, s);
+    return run_path(ctx, a, true, [iters](disco_ctx* x, const PathArgs& b, Steps& st) { iterated_steps(x, b, iters, st); }, s);
 }

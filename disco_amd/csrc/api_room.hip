@@ -5,7 +5,7 @@ using namespace disco;
 using namespace disco_host;
 
 // Wide shapes (P = M + K - 1 > 8), all nodes of a room on this GPU, mask_for_z = 'local', step-1 partial sums of THIS X with
-// THIS mask still in `scratch`: z of every node AND the step-2 partial sums of every node from ONE pass over X (k_room.h),
+// THIS mask still kept (step1_held): z of every node AND the step-2 partial sums of every node from ONE pass over X (k_room.h),
 // instead of disco_apply + cov_partials; room_cov_ok says whether the shape and the context's state qualify.
 namespace disco_host {
 bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask) {
@@ -17,7 +17,7 @@ bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask) {
 #undef X_
     const bool want = ctx->opt[DISCO_OPT_ROOM_COV] != 0;
     if (!want || !shape || M + K - 1 <= 8 || sharded(ctx) || !X || !mask) return false;
-    if (!(ctx->loc_M == M && ctx->loc_X == X && ctx->loc_mask == mask)) return false;       // the leading M x M block must be step 1's
+    if (!step1_held(ctx, X, mask)) return false;                                             // the leading M x M block must be step 1's
     return (long long)K * ctx->T * ctx->F * M <= 0x0fffffffLL;                               // 32-bit BYTE offsets inside a room (8 B per element)
 }
 
@@ -26,21 +26,22 @@ bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask) {
 int room_chunks(const disco_ctx*) { return 2; }
 
 int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z,
-                             int* chunks_out, disco_stream s, bool store_z) {
+                      disco_stream s, bool store_z) {
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics, K = c.nodes, P = M + K - 1;
     if (!w_loc || !z || !room_cov_ok(ctx, X, mask)) return fail(ctx, DISCO_E_ARG, "room covariance: shape / state does not qualify");
     const int chunks = room_chunks(ctx);
     const long long G = (long long)c.rooms * K;
     const int NP = P * (P + 1) / 2;
-    int rc = ensure_scratch2(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4));
+    int rc = 0;
+    float4* part = partials_begin(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4), true, &rc);
     if (rc) return rc;
     RoomArgs a;
     a.X = (const c32*)X;
     a.mask = mask;
     a.w = (const c32*)w_loc;
     a.z = (c32*)z;
-    a.part = (float4*)ctx->scratch2;
+    a.part = part;
     a.T = ctx->T;
     a.F = ctx->F;
     a.chunks = chunks;
@@ -57,10 +58,7 @@ int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, con
         if (items >= 64) nwg = std::max(64u, nwg / 64 * 64);
         if (!launch_room_s8(M, K, nwg, (hipStream_t)s, a)) return fail(ctx, DISCO_E_UNSUPPORTED, "room covariance: shape not instantiated");
     }
-    *chunks_out = chunks;
-    ctx->pending_chunks = chunks;
-    ctx->pending_P = P;
-    ctx->pending_skiploc = 1;
+    partials_commit(ctx, chunks, P, true);
     return check_launch(ctx, "k_room_cov");
 }
 }  // namespace disco_host

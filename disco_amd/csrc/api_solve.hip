@@ -86,21 +86,22 @@ extern "C" int disco_gevd_mwf_r1(disco_ctx* ctx, const disco_c32* Rss, const dis
 extern "C" int disco_gevd_mwf_r1_pending(disco_ctx* ctx, float mu, disco_c32* w, disco_c32* t1, disco_stream s) {
     DISCO_ENTER(ctx);
     if (!w) return fail(ctx, DISCO_E_ARG, "disco_gevd_mwf_r1_pending: null argument");
-    if (ctx->pending_chunks < 1 || !ctx->scratch)
+    PendingSums ps;
+    if (!partials_pending(ctx, &ps))
         return fail(ctx, DISCO_E_ARG, "disco_gevd_mwf_r1_pending: no covariance call has left partial sums in this context");
     SolveSrc src;
     src.Rss = nullptr;
     src.Rnn = nullptr;
-    src.part = (const float4*)(ctx->pending_skiploc ? ctx->scratch2 : ctx->scratch);
+    src.part = ps.part;
     src.F = ctx->F;
-    src.chunks = ctx->pending_chunks;
+    src.chunks = ps.blocks;
     // The partial sums go to the solvers UNSCALED (round 5): w and t1 do not change when Rxx and Rnn are scaled together, and without the
     // multiplication by 1 / T an entry that arrives as one float32 block (the fused step-2 pass leaves one block per node) or as the (hi, lo)
     // pair of a float64 total (k_cov_loc_f64, the room pass) reaches the float64 arithmetic exactly as it was summed; a product with 1 / T
     // cost every entry a rounding (k_solve_dpp.h)
     src.inv_T = 1.0f;
-    src.part_loc = ctx->pending_skiploc ? (const float4*)ctx->scratch : nullptr;
-    src.chunks_loc = ctx->pending_skiploc ? ctx->loc_chunks : 0;
-    src.M_loc = ctx->pending_skiploc ? ctx->loc_M : 0;
-    return solve_dispatch(ctx, src, (int64_t)ctx->cfg.rooms * ctx->Kl * ctx->F, ctx->pending_P, mu, w, t1, s);
+    src.part_loc = ps.part_loc;
+    src.chunks_loc = ps.blocks_loc;
+    src.M_loc = ps.M_loc;
+    return solve_dispatch(ctx, src, (int64_t)ctx->cfg.rooms * ctx->Kl * ctx->F, ps.P, mu, w, t1, s);
 }

@@ -19,11 +19,10 @@ int step2_chunks(const disco_ctx* ctx, int tiles_plus_1) {
     return (int)c;
 }
 
-// skiploc: the caller guarantees that `scratch` still holds the step-1 partial sums of THIS X with THIS mask (only
-// disco_tango_enhance can know); the leading M x M block is then neither accumulated nor written and the step-2 partials
-// go to `scratch2`.
+// skiploc: the caller has checked that the step-1 partial sums of THIS X with THIS mask are still kept (step1_held); the leading
+// M x M block is then neither accumulated nor written and the step-2 partials go to the tail block.
 int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
-                       disco_c32* z_out, int* chunks_out, disco_stream s, bool skiploc) {
+                       disco_c32* z_out, disco_stream s, bool skiploc) {
     if (!X || !mask_w || !w_loc) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: null argument");
     if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "fused kernels need every node of a room on this GPU (node shard active)");
     const disco_cfg& c = ctx->cfg;
@@ -35,7 +34,7 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     const int NP = P * (P + 1) / 2;
     const size_t need = (size_t)G * chunks * ctx->F * NP * sizeof(float4);
     int rc = 0;
-    rc = skiploc ? ensure_scratch2(ctx, need) : ensure_scratch(ctx, need);
+    float4* part = partials_begin(ctx, need, skiploc, &rc);
     if (rc) return rc;
     Step2Args a;
     a.X = (const c32*)X;
@@ -44,7 +43,7 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     a.w_glo = nullptr;
     a.z_out = (c32*)z_out;
     a.yf = nullptr;
-    a.part = (float4*)(skiploc ? ctx->scratch2 : ctx->scratch);
+    a.part = part;
     a.K = K;
     a.T = ctx->T;
     a.F = ctx->F;
@@ -66,11 +65,7 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     DISCO_FOR_MKR(X_)
 #undef X_
     if (!launched) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: unsupported (M, K) combination");
-    *chunks_out = chunks;
-    ctx->pending_chunks = chunks;
-    ctx->pending_P = P;
-    ctx->pending_skiploc = skiploc ? 1 : 0;
-    if (!skiploc) ctx->loc_M = 0;
+    partials_commit(ctx, chunks, P, skiploc);
     return check_launch(ctx, "k_step2_cov_fused");
 }
 
@@ -79,19 +74,17 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
 extern "C" int disco_step2_cov_fused_reuse(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
                                            disco_c32* z_out, disco_stream s) {
     DISCO_ENTER(ctx);
-    if (ctx->loc_M != ctx->cfg.mics || ctx->cfg.nodes < 2 || ctx->Kl != ctx->cfg.nodes)
+    if (!step1_any(ctx) || ctx->cfg.nodes < 2 || ctx->Kl != ctx->cfg.nodes)
         return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused_reuse: no step-1 partial sums of disco_stft_cov_fused are held by this context");
-    if (ctx->loc_X != X || ctx->loc_mask != mask_w)
+    if (!step1_held(ctx, X, mask_w))
         return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused_reuse: X / mask_w are not the arrays the held step-1 partial sums were computed from");
-    int chunks = 1;
-    return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, &chunks, s, true);
+    return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, true);
 }
 extern "C" int disco_step2_cov_fused(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
                                      disco_c32* z_out, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: Rss and Rnn must both be given or both be NULL");
-    int chunks = 1;
-    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, &chunks, s);
+    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s);
     if (rc || !Rss) return rc;
-    return cov_finalize(ctx, chunks, ctx->cfg.mics + ctx->cfg.nodes - 1, Rss, Rnn, s);
+    return cov_finalize(ctx, Rss, Rnn, s);
 }

@@ -59,8 +59,7 @@ int stft_cov_chunks(const disco_ctx* ctx, int* runw_out) {
 // store = false (internal, single-node path): the spectra are not written (X may be NULL); only for shapes the fused kernel takes
 // zero_beyond = false (internal, per-room lengths): the frames of X beyond a room's clip are left unwritten -- only for a caller whose every
 // reader of X knows the lengths (the fused route of disco_tango_enhance)
-int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, int* chunks_out, disco_stream s, bool store,
-                      bool zero_beyond) {
+int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store, bool zero_beyond) {
     if (!y || !mask_z || (store && !X)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: null argument");
     // (works on a node shard too: nothing in this pass looks beyond one node -- X, masks and partial sums then hold the shard's Kl nodes per room)
     const disco_cfg& c = ctx->cfg;
@@ -74,37 +73,32 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
         if (!store) return fail(ctx, DISCO_E_UNSUPPORTED, "stft_cov without store: shape needs the staged kernels");
         int rc0 = STAGE(ctx, s, "stft", disco_stft(ctx, y, (int64_t)c.rooms * ctx->Kl, M, X, s));
         if (rc0) return rc0;
-        return STAGE(ctx, s, "cov1", cov_partials(ctx, X, mask_z, nullptr, nullptr, 0, M, chunks_out, s));
+        return STAGE(ctx, s, "cov1", cov_partials(ctx, X, mask_z, nullptr, nullptr, 0, M, s));
     }
     const long long G = (long long)c.rooms * ctx->Kl;
     int runw = 0;
     const int chunks = stft_cov_chunks(ctx, &runw);
     const int NP = M * (M + 1) / 2;
-    int rc = ensure_scratch(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4));
+    int rc = 0;
+    float4* part = partials_begin(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4), false, &rc);
     if (rc) return rc;
     if (G * chunks > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: batch too large");
     const dim3 grid((unsigned)(G * chunks));
     const bool ok = !store
         ? STAGE(ctx, s, "stft_cov1_nostore", c.n_fft == 512
-            ? (launch_stft_cov<512, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
+            ? (launch_stft_cov<512, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, part, ctx->d_win, ctx->d_tw, c.length,
                                            ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0))
-            : (launch_stft_cov<1024, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
+            : (launch_stft_cov<1024, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, part, ctx->d_win, ctx->d_tw, c.length,
                                             ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)))
         : STAGE(ctx, s, "stft_cov1", c.n_fft == 512
-        ? launch_stft_cov<512>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
+        ? launch_stft_cov<512>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
                                ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)
-        : launch_stft_cov<1024>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, (float4*)ctx->scratch, ctx->d_win, ctx->d_tw, c.length,
+        : launch_stft_cov<1024>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
                                 ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0));
     if (!ok) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: unsupported mic count");
-    *chunks_out = chunks;
-    ctx->pending_chunks = chunks;
-    ctx->pending_P = M;
-    ctx->pending_skiploc = 0;
-    ctx->loc_chunks = chunks;          // kept for a possible re-use by step 2 of the same disco_tango_enhance call
-    ctx->loc_M = M;
-    ctx->loc_X = X;
-    ctx->loc_mask = mask_z;
-    if (!store || sharded(ctx)) ctx->loc_M = 0;       // nothing to pair these partial sums with later (a shard runs the staged step 2)
+    partials_commit(ctx, chunks, M, false);
+    // kept for a possible re-use by step 2, unless there is nothing to pair these sums with later (no spectra; a shard runs the staged step 2)
+    if (store && !sharded(ctx)) step1_keep(ctx, X, mask_z);
     return check_launch(ctx, "k_stft_cov");
 }
 
@@ -114,8 +108,7 @@ extern "C" int disco_stft_cov_fused(disco_ctx* ctx, const float* y, const float*
                                     disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: Rss and Rnn must both be given or both be NULL");
-    int chunks = 1;
-    int rc = stft_cov_partials(ctx, y, mask_z, X, &chunks, s);
+    int rc = stft_cov_partials(ctx, y, mask_z, X, s);
     if (rc || !Rss) return rc;
-    return cov_finalize(ctx, chunks, ctx->cfg.mics, Rss, Rnn, s);
+    return cov_finalize(ctx, Rss, Rnn, s);
 }

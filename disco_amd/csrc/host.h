@@ -37,52 +37,78 @@ struct OptionInfo {
 const OptionInfo* option_table();
 }  // namespace disco_host
 
+// a library-owned device allocation that only ever grows (disco_host::grow); freed by disco_destroy
+struct DevBlock {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// ---- the covariance partial sums a context holds between calls -----------------------------------------------------------------------
+// Every covariance pass (k_stft_cov, k_cov*, k_cov_wide, k_step2_cov_fused, k_room_cov) leaves UNFINISHED sums -- per node and bin, `blocks`
+// blocks of P (P + 1) / 2 float4 -- in one of two context-owned blocks, and two records say what is in them.  Nothing outside the functions
+// declared below (api_partials.hip) touches the fields.
+//   full, tail   The full block takes sums that hold the whole triangle.  The tail block takes step-2 sums that LACK their leading M x M
+//                block, because the kept step-1 sums in the full block are that block (k_step2_cov_fused<.., true>, k_cov_split_lds<..,
+//                true>, k_room_cov): one pass less over the M x M pairs, and the two must not share a block.
+//   pending      what the last producer left for disco_gevd_mwf_r1_pending / cov_finalize: blocks (0 = nothing), P, and whether it
+//                sits in the tail block.  Pending in the tail block implies kept step-1 sums in the full block.
+//   kept step 1  the full block holds step-1 sums (P = M) of all nodes of every room, computed from the arrays X and mask: M (0 = it
+//                does not), blocks, and the two arrays, whose IDENTITY is what grants a re-use (step1_held).
+// What ends a record:
+//   * a producer writing the full block ends the kept step-1 record (partials_commit) unless it re-establishes it (step1_keep);
+//   * a block that has to GROW is freed: growing the full block forgets both records, growing the tail block drops only a pencil pending
+//     in it -- the step-1 sums sit in the full block, and the caller has already decided its re-use from them (partials_begin).  So a
+//     staged-API caller who makes a block grow between a covariance call and its solve gets "no covariance call has left partial sums",
+//     not a solve of a fresh block;
+//   * disco_set_tuning and disco_set_lengths forget both records (partials_forget): sums of another launch geometry or of other clip
+//     lengths must neither be solved nor paired with;
+//   * disco_set_node_shard drops the pending record only (pending_drop): the pending solve sizes its batch by the shard.  The kept step-1
+//     record stays: it is only ever made with every node here, and every reader of it refuses under a shard.
+struct Partials {
+    DevBlock full, tail;
+    int pend_blocks = 0, pend_P = 0;
+    bool pend_tail = false;
+    int loc_blocks = 0, loc_M = 0;
+    const void *loc_X = nullptr, *loc_mask = nullptr;
+};
+
 struct disco_ctx {
-    disco_cfg cfg;
-    int T, F;
-    float* d_win;
-    c32* d_tw;
-    void* own_ws;
-    size_t own_ws_bytes;
-    void* scratch;            // covariance chunk partials (grown on demand)
-    size_t scratch_bytes;
-    int pending_chunks, pending_P;   // geometry of the partials currently in `scratch` (0 = none)
-    void* scratch2;                  // step-2 partials when the step-1 ones in `scratch` are re-used (SKIPLOC)
-    size_t scratch2_bytes;
-    int loc_chunks, loc_M;           // geometry of the step-1 partials kept in `scratch` for that re-use
-    const void *loc_X, *loc_mask;    // the STFT / mask arrays those step-1 partials were computed from (identity check of the re-use)
-    int pending_skiploc;             // the pending step-2 partials (scratch2) lack their leading loc_M x loc_M block
-    const void* ref_ws;              // workspace in which a disco_tango_reference(steps = 1) call left its state for a steps = 2 call (else NULL)
-    const void *ref_y, *ref_s, *ref_n;   // ... and the inputs that state was computed from
-    c32* d_tw_conv;                  // 1024-point twiddles of disco_rir_convolve (== d_tw when n_fft is 1024), lazy
-    void* conv_ws;                   // its spectra workspace, lazy
-    size_t conv_ws_bytes;
-    int k0, Kl;                      // node shard: this context holds nodes [k0, k0 + Kl) of every room (default 0, K)
-    int zblk;                        // layout of the exchanged-signal arguments Zs / Zn / Z (disco_set_z_blocks; default K = plain)
-    int tune_runw, tune_cov_chunks, tune_step2_chunks, tune_pairs;   // disco_set_tuning overrides (0 = batch-size heuristic)
-    int opt[DISCO_N_OPTIONS];        // disco_set_option values (DISCO_OPT_*)
-    int n_cu;                        // compute units of cfg.device (the persistent kernels start one workgroup per CU)
-    int geom_rooms;                  // batch size the launch-geometry heuristics look at (cfg.rooms; a half-batch child: its parent's)
+    disco_cfg cfg{};
+    int T = 0, F = 0;
+    float* d_win = nullptr;
+    c32* d_tw = nullptr;
+    DevBlock own_ws;                 // workspace of the whole-path calls that are given none (ensure_own_ws)
+    Partials partials;
+    const void* ref_ws = nullptr;    // workspace in which a disco_tango_reference(steps = 1) call left its state for a steps = 2 call (else NULL)
+    const void *ref_y = nullptr, *ref_s = nullptr, *ref_n = nullptr;   // ... and the inputs that state was computed from
+    c32* d_tw_conv = nullptr;        // 1024-point twiddles of disco_rir_convolve (== d_tw when n_fft is 1024), lazy
+    DevBlock conv_ws;                // its spectra workspace, lazy
+    int k0 = 0, Kl = 0;              // node shard: this context holds nodes [k0, k0 + Kl) of every room (default 0, K)
+    int zblk = 0;                    // layout of the exchanged-signal arguments Zs / Zn / Z (disco_set_z_blocks; default K = plain)
+    int tune_runw = 0, tune_cov_chunks = 0, tune_step2_chunks = 0, tune_pairs = 0;   // disco_set_tuning overrides (0 = batch-size heuristic)
+    int opt[DISCO_N_OPTIONS] = {};   // disco_set_option values (DISCO_OPT_*)
+    int n_cu = 0;                    // compute units of cfg.device (the persistent kernels start one workgroup per CU)
+    int geom_rooms = 0;              // batch size the launch-geometry heuristics look at (cfg.rooms; a half-batch child: its parent's)
     // two half-batch children (rooms split [0, R/2) and [R/2, R)) + the second stream / events of the overlapped whole-path calls
     // (DISCO_OPT_OVERLAP_SOLVES): one half's solves run beside the other half's streaming kernels.  NULL when not in use.
-    disco_ctx* half[2];
-    disco_ctx* parent;               // set in a child
-    hipStream_t side_stream;
-    hipEvent_t ev_fork, ev_join;
+    disco_ctx* half[2] = {nullptr, nullptr};
+    disco_ctx* parent = nullptr;     // set in a child
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // per-stage hipEvent timers of the whole-path entry points (disco_stage_timing / disco_stage_report)
     struct StageRec {
         char name[32];
         std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
     };
-    bool stage_on;
+    bool stage_on = false;
     std::vector<StageRec> stages;
     // per-room clip lengths (disco_set_lengths).  d_lens is what the kernels receive: NULL for the uniform batch, else cfg.rooms ints on
     // the device -- the context's own block (d_lens_own, allocated by the first disco_set_lengths and rewritten in place by later ones),
     // or, in a half-batch child, its slice of the parent's block.  h_lens is the host copy (empty = none).
     std::vector<int32_t> h_lens;
-    int* d_lens;
-    int* d_lens_own;
-    char err[512];
+    int* d_lens = nullptr;
+    int* d_lens_own = nullptr;
+    char err[512] = "";
 };
 
 #define HIPCHK(ctx, call)                                                                       \
@@ -211,10 +237,31 @@ int cov1_f64_chunks(const disco_ctx* ctx);
 int step2_chunks(const disco_ctx* ctx, int tiles_plus_1);
 int stft_cov_chunks(const disco_ctx* ctx, int* runw_out);
 
-// library-owned device memory
-int ensure_scratch(disco_ctx* ctx, size_t bytes);
-int ensure_scratch2(disco_ctx* ctx, size_t bytes);
+// library-owned device memory (api_partials.hip)
+int grow(disco_ctx* ctx, DevBlock& b, size_t need);       // no-op when large enough, else free + allocate: the contents are gone
+int ensure_own_ws(disco_ctx* ctx, size_t bytes);          // ... of own_ws; a steps = 1 state of disco_tango_reference goes with the freed block
 int reserve_scratch(disco_ctx* ctx);
+// the partial sums (struct Partials above)
+// a producer, before its launch: the block it writes (tail: the tail block), `bytes` large; NULL with *rc set when that fails
+float4* partials_begin(disco_ctx* ctx, size_t bytes, bool tail, int* rc);
+// ... after it: what it left.  Sums in the full block end the kept step-1 record; a step-1 producer re-establishes it with step1_keep
+void partials_commit(disco_ctx* ctx, int blocks, int P, bool tail);
+void step1_keep(disco_ctx* ctx, const void* X, const void* mask);     // the sums just committed are step-1 sums of X with mask
+bool step1_any(const disco_ctx* ctx);                                 // step-1 sums of this context's M are kept
+bool step1_held(const disco_ctx* ctx, const void* X, const void* mask);   // ... and were computed from THESE arrays: the re-use guard
+void pending_drop(disco_ctx* ctx);
+void partials_forget(disco_ctx* ctx);
+int partials_reserve(disco_ctx* ctx, size_t full_bytes, size_t tail_bytes);
+size_t partials_bytes(const disco_ctx* ctx);
+// what the pending record hands its readers: the blocks of the pencil and, when they lack the leading M_loc x M_loc block, the kept
+// step-1 blocks that are it (else NULL, 0, 0).  false: nothing is pending
+struct PendingSums {
+    const float4* part;
+    int blocks, P;
+    const float4* part_loc;
+    int blocks_loc, M_loc;
+};
+bool partials_pending(const disco_ctx* ctx, PendingSums* out);
 // half-batch children of the overlapped whole-path calls: created when the batch is large enough (or the option forces it)
 int ensure_halves(disco_ctx* ctx);
 bool overlap_applies(const disco_ctx* ctx);
@@ -230,16 +277,16 @@ int istft_any(disco_ctx* ctx, const disco_c32* Z, int64_t n_sig, float* out, int
 int lengths_sig_per_room(disco_ctx* ctx, int64_t n_sig, const char* who, int* sig_per_room);
 
 // stages (each leaves its partial sums pending in the context; see the definitions)
-int cov_finalize(disco_ctx* ctx, int chunks, int P, disco_c32* Rss, disco_c32* Rnn, disco_stream s);
+int cov_finalize(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s);      // of the pending sums (whole triangle, full block)
 int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn, int mask_remote, int P,
-                 int* chunks_out, disco_stream s, bool skiploc = false);
+                 disco_stream s, bool skiploc = false);
 bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask);
-int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, int* chunks_out,
-                      disco_stream s, bool store_z = true);
-int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, int* chunks_out, disco_stream s,
-                      bool store = true, bool zero_beyond = true);
-int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out, int* chunks_out,
-                       disco_stream s, bool skiploc = false);
+int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, disco_stream s,
+                      bool store_z = true);
+int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store = true,
+                      bool zero_beyond = true);
+int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out, disco_stream s,
+                       bool skiploc = false);
 int stft_apply_istft(disco_ctx* ctx, const float* y, const disco_c32* w, float* out, disco_stream s);
 bool step2_apply_istft_ok(const disco_ctx* ctx);
 bool apply_istft_wide_ok(const disco_ctx* ctx);
