@@ -272,24 +272,47 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, 2) void k_stft_
     }
 }
 
-// tf_mask (dnn/utils.py:57-67) on one bin.  v_sqrt_f32 / v_rcp_f32 (1 ulp) instead of the IEEE div/sqrt expansions:
-// ~12 instructions instead of ~60 per bin, error 2-3 ulp on a mask that is compared at 1e-5.
+// tf_mask (dnn/utils.py:57-67) on one bin, right wherever the reference's float32 arithmetic is: over the whole float32 range of the
+// inputs, with inf and NaN where np.abs / the float32 division put them and nowhere else.
 __device__ __forceinline__ float ipow(float r, int p) {
     float m = r;
     for (int i = 1; i < p; ++i) m *= r;
     return p == 0 ? 1.f : m;
 }
+// |z| as np.abs(complex64) (a hypot): both parts are scaled by the power of two of the larger one before they are squared, so the
+// sum of squares stays in [1/4, 2) -- no overflow above 1.8e19, no underflow below 1e-19, and v_sqrt_f32 (1 ulp, flushes
+// denormals) never sees a denormal.  The scaling is exact; inf stays inf, a NaN part gives NaN, |0| = 0.  The larger part is squared
+// first, so |S| and |i S| are one number however the compiler contracts the sum.
+__device__ __forceinline__ float cmag(c32 z) {
+    const float a = fabsf(z.x), b = fabsf(z.y);
+    const bool sw = a < b;                                          // not fmaxf / fminf: they would drop a NaN part
+    const float hi = sw ? b : a, lo = sw ? a : b;
+    int e;
+    (void)frexpf(hi, &e);                                           // 0 for 0, inf and NaN
+    const float x = ldexpf(hi, -e), y = ldexpf(lo, -e);
+    return ldexpf(__builtin_amdgcn_sqrtf(x * x + y * y), e);        // overflows to inf where the reference's hypot does
+}
 __device__ __forceinline__ float tf_mask_value(c32 S, c32 Nn, int mask_type, int mask_pow, float thr_lin) {
-    const float as = __builtin_amdgcn_sqrtf(S.x * S.x + S.y * S.y);
-    if (mask_type == DISCO_MASK_IAM) {
-        const c32 y = cadd(S, Nn);
-        return ipow(as * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(y.x * y.x + y.y * y.y)), mask_pow);
+    const c32 O = mask_type == DISCO_MASK_IAM ? cadd(S, Nn) : Nn;           // the denominator: |S + N| or |N|
+    const float ss = S.x * S.x + S.y * S.y, so = O.x * O.x + O.y * O.y;
+    // The plain route -- v_sqrt_f32 of the sum of squares, v_rcp_f32 (1 ulp each) -- where both sums of squares lie within 2^+-100: no
+    // overflow, no underflow, no denormal reaches either instruction, the EPS clamp (2^-52 < 2^-50) cannot bind, the quotient is normal.
+    // Everywhere else, and for 'ibm' always: the scaled magnitudes and an IEEE division, the reference's own -- v_rcp_f32 flushes a denormal
+    // reciprocal (|N| above 8.5e37) to zero, and its 1-ulp error decides an exact tie |S| = |N| of 'ibm' either way (a quarter of them wrongly).
+    float q;
+    if (mask_type != DISCO_MASK_IBM && fminf(ss, so) >= 0x1p-100f && fmaxf(ss, so) <= 0x1p100f) {
+        q = __builtin_amdgcn_sqrtf(ss) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(so));
+    } else {
+        float ao = cmag(O);
+        if (mask_type != DISCO_MASK_IAM) ao = ao < 2.220446049250313e-16f ? 2.220446049250313e-16f : ao;      // np.maximum: a NaN stays a NaN
+        q = cmag(S) / ao;
     }
-    const float an = fmaxf(__builtin_amdgcn_sqrtf(Nn.x * Nn.x + Nn.y * Nn.y), 2.220446049250313e-16f);
-    const float xi = ipow(as * __builtin_amdgcn_rcpf(an), mask_pow);
+    const float xi = ipow(q, mask_pow);
+    if (mask_type == DISCO_MASK_IAM) return xi;
     if (mask_type == DISCO_MASK_IBM) return xi >= thr_lin ? 1.f : 0.f;
-    // xi / (1 + xi); an overflowing xi gives NaN exactly like the reference's inf / inf
-    return xi * __builtin_amdgcn_rcpf(1.f + xi);
+    // xi / (1 + xi); an overflowing xi gives NaN exactly like the reference's inf / inf.  Beyond 2^64 the quotient rounds to 1, and
+    // the reciprocal of 1 + xi would be flushed from 2^126 on: (xi - xi) + 1 is 1 for a finite xi and NaN for inf
+    return xi > 0x1p64f ? (xi - xi) + 1.f : xi * __builtin_amdgcn_rcpf(1.f + xi);
 }
 
 // s_ref, n_ref: [n_sig][L] -> mask [n_sig][T][F]; the pair (s, n) shares one complex FFT.  Streams like k_stft.
