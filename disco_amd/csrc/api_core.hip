@@ -316,6 +316,7 @@ const OptionInfo* option_table() {
         {"solve_thread", "DISCO_SOLVE_THREAD", 1},
         {"fuse_wide_istft", "DISCO_FUSE_WIDE_ISTFT", 1},
         {"online_sq32", "DISCO_ONLINE_SQ32", 1},
+        {"packed_x", "DISCO_PACKED_X", 1},
     };
     return t;
 }

@@ -232,20 +232,27 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
     // per-room lengths: both readers of X on the fused route without yf (k_step2_cov_fused, k_step2_apply_istft) stop at a room's own
     // frames, so the frames of X beyond them need not be written; every other route reads them and finds the zeros it relies on
     const bool x_zeros = !(fused_route(ctx) && !yf && c.n_fft == 512 && step2_apply_istft_ok(ctx));
-    st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, X, s, true, x_zeros); }});
+    // ... and on that branch X never leaves the workspace, so its rows may take the packed layout ("packed_x", k_stft.h k_stft_cov: [T][F - 1][M],
+    // the Nyquist bin in the DC slot): every wave load and store of the three passes over X then covers whole 128-byte lines.  The slot of
+    // X in the workspace keeps its size (the packed array is 1 / F smaller), so one workspace serves both values of the option.
+    const bool packed = !x_zeros && ctx->opt[DISCO_OPT_PACKED_X] != 0;
+    st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, X, s, true, x_zeros, packed); }});
     st.push_back({"solve1", true, solve_pending(w)});
 
     if (fused_route(ctx)) {
         // same mask array in both steps (oracle masks; a DNN mask re-used, tango.py:388-389): the leading M x M block of the
         // step-2 covariances IS the step-1 covariance still held as partial sums -> not recomputed
         st.push_back({"step2_cov", false, [=](disco_stream s) {
-            if (step1_held(ctx, X, mask_w)) return disco_step2_cov_fused_reuse(ctx, X, mask_w, w, z_y, s);
-            return step2_cov_partials(ctx, X, mask_w, w, z_y, s);
+            if (step1_held(ctx, X, mask_w)) {
+                if (packed) return step2_cov_partials(ctx, X, mask_w, w, z_y, s, true, true);
+                return disco_step2_cov_fused_reuse(ctx, X, mask_w, w, z_y, s);
+            }
+            return step2_cov_partials(ctx, X, mask_w, w, z_y, s, false, packed);
         }});
         st.push_back({"solve2", true, solve_pending(w2)});
         if (!yf && c.n_fft == 512) {   // yf not asked for: filter + iSTFT in one pass, yf stays on chip (shapes the kernel takes)
             if (step2_apply_istft_ok(ctx)) {
-                st.push_back({"step2_apply_istft", false, [=](disco_stream s) { return disco_step2_apply_istft_fused(ctx, X, w, w2, out, s); }});
+                st.push_back({"step2_apply_istft", false, [=](disco_stream s) { return step2_apply_istft(ctx, X, w, w2, out, s, packed); }});
                 return;
             }
         }

@@ -8,6 +8,17 @@ using namespace disco_host;
 // ---------------------------------------------------------------------------------------------------------
 // step 2 with the in-register z exchange
 // ---------------------------------------------------------------------------------------------------------
+template <int M, int K>
+static bool launch_step2_cov_packed(const Step2Args& a, bool skiploc, dim3 grid, hipStream_t st) {
+    if constexpr (K >= 2) {
+        if (skiploc) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M, K, true, true>), grid, dim3(64 * K), 0, st, a);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M, K, false, true>), grid, dim3(64 * K), 0, st, a);
+        return true;
+    } else {
+        return false;
+    }
+}
+
 namespace disco_host {
 int step2_chunks(const disco_ctx* ctx, int tiles_plus_1) {
     const long long base = (long long)ctx->geom_rooms * tiles_plus_1;
@@ -21,8 +32,9 @@ int step2_chunks(const disco_ctx* ctx, int tiles_plus_1) {
 
 // skiploc: the caller has checked that the step-1 partial sums of THIS X with THIS mask are still kept (step1_held); the leading
 // M x M block is then neither accumulated nor written and the step-2 partials go to the tail block.
+// packed: X is in the packed workspace layout [R][K][T][F - 1][M] (k_stft.h; K >= 2, 512 points) -- the same z and partial sums.
 int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
-                       disco_c32* z_out, disco_stream s, bool skiploc) {
+                       disco_c32* z_out, disco_stream s, bool skiploc, bool packed) {
     if (!X || !mask_w || !w_loc) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: null argument");
     if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "fused kernels need every node of a room on this GPU (node shard active)");
     const disco_cfg& c = ctx->cfg;
@@ -52,6 +64,13 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     const long long nblk = (long long)c.rooms * (tiles + 1) * chunks;
     if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: batch too large");
     bool launched = false;
+    if (packed && (K < 2 || c.n_fft != 512)) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: the packed layout needs K >= 2 and n_fft = 512");
+    // the packed layout: the shapes the fused route of the whole path takes (K >= 2)
+#define X_(M_, KR_)                                                                                                  \
+    if (!launched && packed && M == M_ && K == KR_ + 1)                                                              \
+        launched = launch_step2_cov_packed<M_, KR_ + 1>(a, skiploc, dim3((unsigned)nblk), (hipStream_t)s);
+    DISCO_FOR_MKR(X_)
+#undef X_
 #define X_(M_, KR_)                                                                                                  \
     if (!launched && M == M_ && K == KR_ + 1) {                                                                      \
         if (skiploc)                                                                                                 \
@@ -85,6 +104,22 @@ extern "C" int disco_step2_cov_fused(disco_ctx* ctx, const disco_c32* X, const f
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: Rss and Rnn must both be given or both be NULL");
     int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s);
+    if (rc || !Rss) return rc;
+    return cov_finalize(ctx, Rss, Rnn, s);
+}
+
+// test-only: the same passes reading X in the packed workspace layout (include/disco_hip.h)
+extern "C" int disco_selftest_step2_cov_packed(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
+                                               disco_c32* z_out, disco_c32* Rss, disco_c32* Rnn, int reuse, disco_stream s) {
+    DISCO_ENTER(ctx);
+    if ((Rss == nullptr) != (Rnn == nullptr) || (reuse && Rss))
+        return fail(ctx, DISCO_E_ARG, "disco_selftest_step2_cov_packed: Rss and Rnn must both be given or both be NULL, and NULL with reuse");
+    if (reuse) {
+        if (!step1_any(ctx) || ctx->cfg.nodes < 2 || ctx->Kl != ctx->cfg.nodes || !step1_held(ctx, X, mask_w))
+            return fail(ctx, DISCO_E_ARG, "disco_selftest_step2_cov_packed: no step-1 partial sums of X / mask_w are held by this context");
+        return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, true, true);
+    }
+    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, false, true);
     if (rc || !Rss) return rc;
     return cov_finalize(ctx, Rss, Rnn, s);
 }

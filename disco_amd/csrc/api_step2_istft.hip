@@ -7,8 +7,15 @@ using namespace disco_host;
 
 template <int M, int K>
 static bool launch_apply_istft(const Step2Args& a, float* out, const float* win, const c32* tw, int L, int bpr, int pairs, dim3 grid,
-                               hipStream_t st, const int* lens) {
+                               hipStream_t st, const int* lens, bool packed) {
     if constexpr (sizeof(ApplyIstftShared<512, M, K>) <= 160 * 1024) {
+        if constexpr (K >= 2) {            // the packed workspace layout: the fused route of the whole path only (K >= 2)
+            if (packed) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_apply_istft<512, M, K, true>), grid, dim3(64 * K), 0, st, a, out, win, tw, L, bpr, pairs, lens);
+                return true;
+            }
+        }
+        if (packed) return false;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_apply_istft<512, M, K>), grid, dim3(64 * K), 0, st, a, out, win, tw, L, bpr, pairs, lens);
         return true;
     } else {
@@ -32,6 +39,11 @@ bool step2_apply_istft_ok(const disco_ctx* ctx) {
 extern "C" int disco_step2_apply_istft_fused(disco_ctx* ctx, const disco_c32* X, const disco_c32* w_loc,
                                              const disco_c32* w_glo, float* out, disco_stream s) {
     DISCO_ENTER(ctx);
+    return step2_apply_istft(ctx, X, w_loc, w_glo, out, s, false);
+}
+
+int disco_host::step2_apply_istft(disco_ctx* ctx, const disco_c32* X, const disco_c32* w_loc, const disco_c32* w_glo, float* out, disco_stream s,
+                                  bool packed) {
     if (!X || !w_loc || !w_glo || !out) return fail(ctx, DISCO_E_ARG, "disco_step2_apply_istft_fused: null argument");
     if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "fused kernels need every node of a room on this GPU (node shard active)");
     const disco_cfg& c = ctx->cfg;
@@ -65,7 +77,7 @@ extern "C" int disco_step2_apply_istft_fused(disco_ctx* ctx, const disco_c32* X,
     if (!tried && M == M_ && K == KR_ + 1) {                                                                         \
         tried = true;                                                                                                \
         launched = launch_apply_istft<M_, KR_ + 1>(a, out, ctx->d_win, ctx->d_tw, c.length, bpr, pairs, dim3((unsigned)nblk), \
-                                                   (hipStream_t)s, ctx->d_lens);                                     \
+                                                   (hipStream_t)s, ctx->d_lens, packed);                             \
     }
     DISCO_FOR_MKR(X_)
 #undef X_

@@ -8,7 +8,7 @@ using namespace disco_host;
 // ---------------------------------------------------------------------------------------------------------
 // STFT + step-1 covariance in one pass
 // ---------------------------------------------------------------------------------------------------------
-template <int N, bool STORE = true>
+template <int N, bool STORE = true, bool PACK = false>
 static bool launch_stft_cov(int M, dim3 grid, hipStream_t st, const float* y, const float* mask, c32* X, float4* part,
                             const float* win, const c32* tw, int L, int T, int pad_mode, int chunks, int runw, const int* lens, int spr,
                             int zero_beyond) {
@@ -16,7 +16,7 @@ static bool launch_stft_cov(int M, dim3 grid, hipStream_t st, const float* y, co
     switch (M) {
 #define C_(M_)                                                                                                          \
     case M_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE, PACK>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
                            chunks, runw, lens, spr, zero_beyond);                                                       \
         return true;
         C_(1) C_(2) C_(3) C_(4) C_(5) C_(6)
@@ -26,7 +26,7 @@ static bool launch_stft_cov(int M, dim3 grid, hipStream_t st, const float* y, co
         switch (M) {
 #define C_(M_)                                                                                                          \
     case M_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE, PACK>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
                            chunks, runw, lens, spr, zero_beyond);                                                       \
         return true;
             C_(7) C_(8)
@@ -59,8 +59,11 @@ int stft_cov_chunks(const disco_ctx* ctx, int* runw_out) {
 // store = false (internal, single-node path): the spectra are not written (X may be NULL); only for shapes the fused kernel takes
 // zero_beyond = false (internal, per-room lengths): the frames of X beyond a room's clip are left unwritten -- only for a caller whose every
 // reader of X knows the lengths (the fused route of disco_tango_enhance)
-int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store, bool zero_beyond) {
+// packed = true (internal; 512 points, stored spectra): X in the packed workspace layout [G][T][F - 1][M] (k_stft.h) -- the same partial sums
+int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store, bool zero_beyond,
+                      bool packed) {
     if (!y || !mask_z || (store && !X)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: null argument");
+    if (packed && (!store || ctx->cfg.n_fft != 512)) return fail(ctx, DISCO_E_UNSUPPORTED, "stft_cov: the packed layout needs n_fft = 512 and stored spectra");
     // (works on a node shard too: nothing in this pass looks beyond one node -- X, masks and partial sums then hold the shard's Kl nodes per room)
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics;
@@ -90,7 +93,10 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
                                            ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0))
             : (launch_stft_cov<1024, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, part, ctx->d_win, ctx->d_tw, c.length,
                                             ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)))
-        : STAGE(ctx, s, "stft_cov1", c.n_fft == 512
+        : STAGE(ctx, s, "stft_cov1", packed
+        ? (launch_stft_cov<512, true, true>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
+                                            ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0))
+        : c.n_fft == 512
         ? launch_stft_cov<512>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
                                ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)
         : launch_stft_cov<1024>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
@@ -109,6 +115,16 @@ extern "C" int disco_stft_cov_fused(disco_ctx* ctx, const float* y, const float*
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: Rss and Rnn must both be given or both be NULL");
     int rc = stft_cov_partials(ctx, y, mask_z, X, s);
+    if (rc || !Rss) return rc;
+    return cov_finalize(ctx, Rss, Rnn, s);
+}
+
+// test-only: the same pass writing X in the packed workspace layout (include/disco_hip.h)
+extern "C" int disco_selftest_stft_cov_packed(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_c32* Rss,
+                                              disco_c32* Rnn, disco_stream s) {
+    DISCO_ENTER(ctx);
+    if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_selftest_stft_cov_packed: Rss and Rnn must both be given or both be NULL");
+    int rc = stft_cov_partials(ctx, y, mask_z, X, s, true, true, true);
     if (rc || !Rss) return rc;
     return cov_finalize(ctx, Rss, Rnn, s);
 }

@@ -27,6 +27,7 @@ enum {
     DISCO_OPT_SOLVE_THREAD,             // "solve_thread": 5 <= P <= 8 solved one THREAD per pencil (k_solve_small.h at one wave per SIMD, AGPRs as the second register file) instead of the LDS group solver
     DISCO_OPT_FUSE_WIDE_ISTFT,          // "fuse_wide_istft": whole-path calls of the wide shapes (P > 8) end in ONE filter + iSTFT pass (k_apply_istft_wide) instead of disco_apply + disco_istft
     DISCO_OPT_ONLINE_SQ32,              // "online_sq32": the online mode's thread solves (P <= 7) square in packed float32 (k_solve_small.h); 0: float64 throughout
+    DISCO_OPT_PACKED_X,                 // "packed_x": the fused route of disco_tango_enhance keeps its workspace X in line-aligned rows [T][F - 1][M], the Nyquist bin in the DC slot (0: the public [T][F][M])
     DISCO_N_OPTIONS
 };
 namespace disco_host {
@@ -284,9 +285,12 @@ bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask);
 int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, disco_stream s,
                       bool store_z = true);
 int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store = true,
-                      bool zero_beyond = true);
+                      bool zero_beyond = true, bool packed = false);
 int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out, disco_stream s,
-                       bool skiploc = false);
+                       bool skiploc = false, bool packed = false);
+// filter + iSTFT of the fused route (disco_step2_apply_istft_fused); packed: X in the packed workspace layout (k_stft.h)
+int step2_apply_istft(disco_ctx* ctx, const disco_c32* X, const disco_c32* w_loc, const disco_c32* w_glo, float* out, disco_stream s,
+                      bool packed);
 int stft_apply_istft(disco_ctx* ctx, const float* y, const disco_c32* w, float* out, disco_stream s);
 bool step2_apply_istft_ok(const disco_ctx* ctx);
 bool apply_istft_wide_ok(const disco_ctx* ctx);

@@ -34,14 +34,42 @@ struct Step2Geom {
     bool nyq;
 };
 
+// DISCO_S2_XCD_MAP: which workgroup does what (a pure permutation: every sum keeps its operands and its order).
+//   0  blockIdx.x = (room, tile, chunk), chunk fastest: the tiles + 1 workgroups of one (room, chunk) are `chunks` apart and land on as many
+//      XCDs (workgroups go round the 8 XCDs in turn)
+//   1  units (room, chunk) in groups of 8; inside a group blockIdx.x = (tile, unit), unit fastest: the tiles + 1 workgroups of a unit are 8
+//      apart -- dispatched together and on ONE XCD, so the lines they share (the mask spans that straddle two tiles, the Nyquist
+//      workgroup's lines) can meet in that XCD's L2.  The last, incomplete group keeps the order (tile, unit) without the alignment.
+//      C3, k_step2_cov_fused<4, 4, true> on packed rows: 25.00 -> 24.61 GB fetched, 4.27 -> 4.14 ms (profiles/s2_xcd_map.txt)
+#ifndef DISCO_S2_XCD_MAP
+#define DISCO_S2_XCD_MAP 1
+#endif
 __device__ __forceinline__ Step2Geom step2_geom(const Step2Args& a, int lane) {
     Step2Geom g;
     const int nbin = a.F - 1, tiles = nbin / 64;
     int bid = blockIdx.x;
-    g.c = bid % a.chunks;
-    bid /= a.chunks;
-    const int tile = bid % (tiles + 1);
-    g.r = bid / (tiles + 1);
+    int tile;
+    if (DISCO_S2_XCD_MAP) {
+        const long long units = (long long)(gridDim.x / (tiles + 1));           // rooms * chunks
+        const long long full = units / 8, grp = bid / (8 * (tiles + 1));
+        long long u;
+        if (grp < full) {
+            const int j = bid % (8 * (tiles + 1));
+            tile = j / 8;
+            u = grp * 8 + j % 8;
+        } else {
+            const int n = (int)(units - full * 8), j = (int)(bid - full * 8 * (tiles + 1));
+            tile = j / n;
+            u = full * 8 + j % n;
+        }
+        g.c = (int)(u % a.chunks);
+        g.r = u / a.chunks;
+    } else {
+        g.c = bid % a.chunks;
+        bid /= a.chunks;
+        tile = bid % (tiles + 1);
+        g.r = bid / (tiles + 1);
+    }
     g.t0 = (int)(((long long)a.T * g.c) / a.chunks);
     g.t1 = (int)(((long long)a.T * (g.c + 1)) / a.chunks);
     g.nyq = tile == tiles;
@@ -72,15 +100,20 @@ constexpr int S2_U_APPLY = DISCO_S2_U_APPLY;    // frames per barrier in the app
 // SKIPLOC: mask_w is the very array step 1 used (oracle masks, or a DNN's mask reused, tango.py:388-389), so the leading
 // M x M block of both step-2 covariances equals the step-1 covariances already sitting in the context as partial sums:
 // those 10 of 28 entry pairs (M = 4, K = 4) are neither accumulated nor written, the solver takes them from step 1.
-template <int M, int K, bool SKIPLOC>
+// PACK: X in the packed workspace layout [R][K][T][F - 1][M] (k_stft.h, k_stft_cov): a tile wave's 64 bins x 8 M bytes start on a 128-byte
+// line in every frame.  The lane of bin 0 takes the real half of slot 0, the Nyquist workgroup the other half; both as (value, +0) where the
+// public layout holds (value, +-0) -- every use multiplies and adds, so no sum changes.  Everything else (mask, z, partial sums) is as ever.
+template <int M, int K, bool SKIPLOC, bool PACK = false>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K) void k_step2_cov_fused(Step2Args a) {
     constexpr int P = M + K - 1, NP = P * (P + 1) / 2, U = S2_U_COV;
     __shared__ c32 zbuf[2][U][K][64];
     const int k = wave_id(), lane = threadIdx.x & 63;
     const Step2Geom gm = step2_geom(a, lane);
     const int T = a.T, F = a.F, f = gm.f;
+    const int FX = PACK ? F - 1 : F, fx = (PACK && gm.nyq) ? 0 : f;      // pitch of an X row in bins, this lane's slot in it
+    const bool x_dc = PACK && !gm.nyq && f == 0, x_ny = PACK && gm.nyq;   // (per lane, fixed for the kernel: selects, no branch in the loop)
     const long long g = gm.r * a.K + k;
-    const c32* Xg = a.X + (g * T * (long long)F) * M;
+    const c32* Xg = a.X + (g * T * (long long)FX) * M;
     const float* mg = a.mask + g * T * (long long)F;
     c32* zg = a.z_out ? a.z_out + g * T * (long long)F : nullptr;
     c32 wl[M];
@@ -105,9 +138,10 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K) void k_step2_cov_fused(S
         for (int u = 0; u < U; ++u) {
             const int t = tu + u * gm.t_stride + gm.t_lane;
             const bool live = t < t1;
-            const long long tf = (long long)(live ? t : t1 - 1) * F + f;      // always a valid frame: loads stay unconditional
+            const long long tv = live ? t : t1 - 1;                          // always a valid frame: loads stay unconditional
+            const long long tf = tv * F + f, tx = tv * FX + fx;
 #pragma unroll
-            for (int i = 0; i < M; ++i) xx[u][i] = Xg[tf * M + i];      // raw: consumed (and zeroed if !live) after the barrier
+            for (int i = 0; i < M; ++i) xx[u][i] = Xg[tx * M + i];      // raw: consumed (and zeroed if !live) after the barrier
             mm[u] = mg[tf];
         }
     };
@@ -120,6 +154,10 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K) void k_step2_cov_fused(S
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = tu + u * gm.t_stride + gm.t_lane;
+            if constexpr (PACK) {
+#pragma unroll
+                for (int i = 0; i < M; ++i) x[u][i] = make_float2(x_ny ? x[u][i].y : x[u][i].x, (x_dc || x_ny) ? 0.f : x[u][i].y);
+            }
             const c32 z = filt_conj<M>(wl, x[u]);
             zbuf[buf][u][k][lane] = z;
             if (t < t1 && zg) zg[(long long)t * F + f] = z;
@@ -335,11 +373,14 @@ struct alignas(16) ApplyIstftShared {
 };
 
 // 2 waves per SIMD is what the 68 kB of LDS allow; stated so that the allocator keeps the prefetch within 256 registers
-template <int N, int M, int K>
+// PACK: X in the packed workspace layout [R][K][T][N / 2][M] (k_stft.h, k_stft_cov): lane 0, which owns both bin 0 and the Nyquist bin,
+// finds both in slot 0, so the Nyquist load is gone and every wave load covers whole 128-byte lines
+template <int N, int M, int K, bool PACK = false>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 : 1) void k_step2_apply_istft(Step2Args a, float* __restrict__ out,
                                                                const float* __restrict__ win, const c32* __restrict__ tw,
                                                                int L, int blocks_per_room, int pairs, const int* __restrict__ lens) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, H = N / 2, EH = E / 2, NJ = EH + 1, P = M + K - 1;
+    constexpr int FX = PACK ? F - 1 : F, NJX = PACK ? EH : NJ;     // bins of a stored row of X, and how many of them a lane loads
     __shared__ ApplyIstftShared<N, M, K> sh;
     const int k = wave_id(), lane = threadIdx.x & 63;
     const long long r = blockIdx.x / blocks_per_room;
@@ -353,7 +394,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
         ola_zero_segments<N>(out + g * (long long)L, s0, 2 * pairs - 1, L, lane);
         return;
     }
-    const c32* Xg = a.X + (g * T * (long long)F) * M;
+    const c32* Xg = a.X + (g * T * (long long)FX) * M;
     // the room's local filters -> LDS (every wave needs all of them only through z; its own row is read per frame)
     if constexpr (K > 1) {
         const c32* src = a.w_loc + (r * K) * (long long)F * M;
@@ -384,9 +425,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
         if constexpr (!PF) return;
 #pragma unroll
         for (int fr = 0; fr < (PF ? 2 : 0); ++fr) {
-            const long long tf0 = (long long)min(tA_ + fr, T - 1) * F;
+            const long long tf0 = (long long)min(tA_ + fr, T - 1) * FX;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
+            for (int j = 0; j < NJX; ++j) {
                 const int f = (j < EH) ? lane + 64 * j : F - 1;
 #pragma unroll
                 for (int i = 0; i < M; ++i) xr[fr][j][i] = Xg[(tf0 + f) * M + i];
@@ -403,8 +444,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
         for (int fr = 0; fr < 2; ++fr) {
             const int t = tA + fr;
             const bool tv = t < T;
-            const long long tf0 = (long long)(tv ? t : T - 1) * F;
+            const long long tf0 = (long long)(tv ? t : T - 1) * FX;
             (void)tf0;
+            c32 x0[PACK ? M : 1];                      // PACK: slot 0 as loaded -- (Re DC, Re Nyquist) in lane 0
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 const int f = (j < EH) ? lane + 64 * j : F - 1;
@@ -412,8 +454,21 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
 #pragma unroll
                 for (int i = 0; i < M; ++i) {
                     c32 v;
-                    if constexpr (PF) v = xr[PF ? fr : 0][PF ? j : 0][i];
-                    else v = Xg[(tf0 + f) * M + i];
+                    if constexpr (PACK) {
+                        if (j < EH) {
+                            if constexpr (PF) v = xr[PF ? fr : 0][PF ? j : 0][i];
+                            else v = Xg[(tf0 + f) * M + i];
+                            if (j == 0) {
+                                x0[PACK ? i : 0] = v;
+                                v.y = lane == 0 ? 0.f : v.y;
+                            }
+                        } else {
+                            v = make_float2(x0[PACK ? i : 0].y, 0.f);     // the Nyquist bin counts in lane 0 only (irfft_pair_pack, zbuf)
+                        }
+                    } else {
+                        if constexpr (PF) v = xr[PF ? fr : 0][PF ? j : 0][i];
+                        else v = Xg[(tf0 + f) * M + i];
+                    }
                     x[i] = v;                          // frames past the signal: clamped (finite) data, their yf is zeroed below
                 }
                 if constexpr (K > 1) {
@@ -460,7 +515,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
 #pragma unroll
             for (int fr = 0; fr < 2; ++fr)
 #pragma unroll
-                for (int j = 0; j < NJ; ++j)
+                for (int j = 0; j < NJX; ++j)
 #pragma unroll
                     for (int i = 0; i < M; ++i) {
                         DISCO_CONSUME(xr[PF ? fr : 0][PF ? j : 0][i].x);

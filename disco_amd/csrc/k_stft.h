@@ -542,7 +542,11 @@ struct alignas(16) StftCovShared {
 #endif
 // STORE = false: the spectra are reduced into the covariances and dropped (single-node path: the filter pass recomputes them
 // from the samples, k_stft_apply_istft, instead of reading 8 M F bytes per node-frame back)
-template <int N, int M, bool STORE = true>
+// PACK: the workspace layout of the whole path's fused route -- rows of F - 1 = N / 2 bins, [T][N / 2][M]: slot 0 of channel i holds
+// (Re X[0][i], Re X[N / 2][i]).  DC and Nyquist of a real frame are real (the untangle gives their imaginary parts as exact zeros), so
+// nothing is lost, and a row is 4 N M bytes -- a whole number of 128-byte lines, where the public row (8 M F bytes) starts 0 / 32 / 64 /
+// 96 bytes into a line.  Only the addresses of the copy-out differ: the fold reads the LDS tile and forms the same sums in the same order.
+template <int N, int M, bool STORE = true, bool PACK = false>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M <= 4) ? DISCO_SC_WPE : 1) void k_stft_cov(const float* __restrict__ x, const float* __restrict__ mask,
                                                                c32* __restrict__ X, float4* __restrict__ part,
                                                                const float* __restrict__ win, const c32* __restrict__ tw,
@@ -551,6 +555,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
     static_assert(STFT_WAVES == 4, "one bin per thread needs 4 waves for 256 bins");
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, EH = E / 2, CHP = (M + 1) / 2, MP = 2 * CHP;
     constexpr int NP = M * (M + 1) / 2;
+    constexpr int FX = PACK ? F - 1 : F;           // bins of a stored row
     constexpr int BPT = (F - 1) / 256;             // bins per thread: 1 (N = 512) or 2 (N = 1024)
     constexpr bool ZT = DISCO_ZTILE != 0;
     constexpr int ZP = stft_cov_zpitch<N>();
@@ -571,8 +576,8 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
         // the frames of this chunk the room does not have: zeros, unless every reader of X knows the lengths itself (zero_beyond = 0: the
         // fused route of the whole path, where X never leaves the workspace -- the zeros would cost what the spectra cost to store)
         if (STORE && zero_beyond && tz0 < tz1) {
-            c32* Xz = X + ((g * T + tz0) * (long long)F) * M;
-            const long long nz = (long long)(tz1 - tz0) * F * M;
+            c32* Xz = X + ((g * T + tz0) * (long long)FX) * M;
+            const long long nz = (long long)(tz1 - tz0) * FX * M;
             for (long long i = tid; i < nz; i += 64 * STFT_WAVES) Xz[i] = make_float2(0.f, 0.f);
         }
         if (tb >= Tr) {                            // a chunk wholly in the padding: zero sums, no sample or mask touched
@@ -679,8 +684,35 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
         for (int ww = 0; ww < STFT_WAVES; ++ww) {
             const int t2 = tb + ww * runw + it;
             if (t2 < min(Tr, tb + (ww + 1) * runw)) {         // workgroup-uniform
-                c32* Xo = STORE ? X + ((g * T + t2) * (long long)F) * M : nullptr;
-                if (STORE && (M & 1) == 0 && !(DISCO_SC_EXP & 4)) {
+                c32* Xo = STORE ? X + ((g * T + t2) * (long long)FX) * M : nullptr;
+                if constexpr (STORE && PACK && (M & 1) == 0 && !(DISCO_SC_EXP & 4)) {
+                    // packed rows begin on a line: a plain linear copy of (F - 1) * M / 2 granules; the granules of bin 0 carry the
+                    // Nyquist bin's real parts where the (zero) imaginary parts of DC would go
+                    float4* dst = reinterpret_cast<float4*>(Xo);
+                    for (int i = tid; i < (F - 1) * CHP; i += 64 * STFT_WAVES) {
+                        float4 q4;
+                        if constexpr (ZT) {
+                            const int f = i / CHP, pp = i - f * CHP;
+                            const c32* zp = zplane(ww, pp);
+                            const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
+                            const c32 a = cadd_conj(z, zc), b = csub_conj_mi(z, zc);
+                            q4 = make_float4(a.x, a.y, b.x, b.y);
+                            if (f == 0) {
+                                const c32 zq = zp[N / 2];
+                                q4.y = cadd_conj(zq, zq).x;
+                                q4.w = csub_conj_mi(zq, zq).x;
+                            }
+                        } else {
+                            q4 = reinterpret_cast<const float4*>(xrow(ww, 0))[i];
+                            if (i < CHP) {
+                                const float4 qn = reinterpret_cast<const float4*>(xrow(ww, F - 1))[i];
+                                q4.y = qn.x;
+                                q4.w = qn.z;
+                            }
+                        }
+                        store_stream16(&dst[i], q4);
+                    }
+                } else if (STORE && (M & 1) == 0 && !(DISCO_SC_EXP & 4)) {
                     // even M: the tile row IS the X row (F*M complex, contiguous) -> straight 16-B-per-lane copy, every
                     // wave store covers 1 KiB of consecutive bytes (a per-bin store would touch each 128-B line twice)
                     // The rows are 8 * M * F bytes long (8224 for M = 4), so they start 0 / 32 / 64 / 96 bytes into a 128-byte line: the
@@ -721,8 +753,13 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
                         }
                     }
                     if (STORE && (M & 1) != 0) {
+                        if (PACK && f == 0) {           // the real parts only: the other half of slot 0 is the Nyquist threads' (below)
 #pragma unroll
-                        for (int i = 0; i < M; ++i) Xo[(long long)f * M + i] = xv[i];
+                            for (int i = 0; i < M; ++i) reinterpret_cast<float*>(Xo)[2 * i] = xv[i].x;
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < M; ++i) Xo[(long long)f * M + i] = xv[i];
+                        }
                     }
                     const float m = mv[ww][b], mc = 1.f - m;
                     if (!(DISCO_SC_EXP & 2)) cov_accumulate_shared<M>(xv, m * m, mc * mc, acc_s[b], acc_n[b]);
@@ -730,12 +767,15 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
                 }
                 // Nyquist bin
                 if (STORE && (M & 1) != 0 && tid < M) {
+                    c32 xq;
                     if constexpr (ZT) {
                         const c32 zq = zplane(ww, tid >> 1)[N / 2];
-                        Xo[(long long)(F - 1) * M + tid] = (tid & 1) ? csub_conj_mi(zq, zq) : cadd_conj(zq, zq);
+                        xq = (tid & 1) ? csub_conj_mi(zq, zq) : cadd_conj(zq, zq);
                     } else {
-                        Xo[(long long)(F - 1) * M + tid] = xrow(ww, F - 1)[tid];
+                        xq = xrow(ww, F - 1)[tid];
                     }
+                    if constexpr (PACK) reinterpret_cast<float*>(Xo)[2 * tid + 1] = xq.x;
+                    else Xo[(long long)(F - 1) * M + tid] = xq;
                 }
                 if (tid < 2 * NP) {
                     const float m = (tid & 1) ? 1.f - mny[ww] : mny[ww];

@@ -364,7 +364,7 @@ class Engine:
         self._chk(self.lib.disco_set_tuning(self.ctx, stft_frames_per_wave, cov_chunks, step2_chunks, istft_pairs))
         self._tuning = (int(stft_frames_per_wave), int(cov_chunks), int(step2_chunks), int(istft_pairs))
 
-    OPTION_KEYS = ('room_cov', 'overlap_solves', 'solve_thread', 'solve_dpp', 'online_sq32', 'fuse_wide_istft')
+    OPTION_KEYS = ('room_cov', 'overlap_solves', 'solve_thread', 'solve_dpp', 'online_sq32', 'fuse_wide_istft', 'packed_x')
 
     def sibling(self, rooms, first_room=0):
         """A second engine for `rooms` rooms of the same problem: every field of the configuration (hop, reference microphone, mask

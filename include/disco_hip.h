@@ -180,6 +180,12 @@ int  disco_set_tuning(disco_ctx* ctx, int stft_frames_per_wave, int cov_chunks, 
  *                         filter + iSTFT pass (csrc/k_fused.h k_apply_istft_wide, stage "apply2_istft": the filtered spectra stay on chip, and are
  *                         written only when the caller asks for yf) instead of disco_apply + disco_istft ("apply2" + "istft": what the ABI's
  *                         stage calls and a node shard run)
+ *   "packed_x"           (DISCO_PACKED_X, 1) disco_tango_enhance on the on-chip-exchange route when yf is not asked for (nodes >= 2, M + K - 1 <= 8,
+ *                         512-point STFT: stages "stft_cov1", "step2_cov", "step2_apply_istft") keeps the spectra, which then never leave the
+ *                         workspace, in rows of F - 1 bins -- [R][K][T][F - 1][M], slot 0 of a channel = (Re X[0], Re X[F - 1]): DC and Nyquist of
+ *                         a real frame are real.  A row is then a whole number of 128-byte lines (the public row of 8 M F bytes is not), so no
+ *                         wave load or store of the three passes straddles one.  Same results (np.array_equal); the workspace size does not
+ *                         depend on the option; 0: the public layout [T][F][M] there too.  Every argument X of the ABI is [T][F][M] in any case
  * Routes that earlier rounds measured slower or less accurate and kept "as a record" are gone from the library (round 5): the filter +
  * iSTFT pass from the samples, the register-staged room pass, the mixed-precision group solver, 4 time sub-chunks in the room pass, the
  * float32 step-1 statistics of the wide shapes, the solves-only side stream.  Their measurements are in profiles/.
@@ -587,6 +593,16 @@ int disco_selftest_dpp(disco_ctx* ctx, const double* a, const double* b, int64_t
  * 256 -> out_hw, out_ref: [n / 4][DISCO_ROOM_SELFTEST_OPS] float (one row per lane).  Bit equality is what is asserted.  ctx may be NULL. */
 #define DISCO_ROOM_SELFTEST_OPS 6
 int disco_selftest_room(disco_ctx* ctx, const float* src, int64_t n, float* out_hw, float* out_ref, disco_stream s);
+
+/* The kernels of the "packed_x" layout one by one (tests; no reference counterpart).  X here -- and only here -- is the PACKED array
+ * [R][K][T][F - 1][M] complex64, slot 0 of a channel = (Re X[0], Re X[F - 1]); everything else is as in the call named.  512-point STFT.
+ *   disco_selftest_stft_cov_packed    disco_stft_cov_fused writing X packed (it keeps the step-1 sums for X / mask_z like that call)
+ *   disco_selftest_step2_cov_packed   reuse == 0: disco_step2_cov_fused reading X packed; reuse != 0: disco_step2_cov_fused_reuse (Rss, Rnn
+ *                                     must be NULL; solve with disco_gevd_mwf_r1_pending).  nodes >= 2 */
+int disco_selftest_stft_cov_packed(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_c32* Rss, disco_c32* Rnn,
+                                   disco_stream s);
+int disco_selftest_step2_cov_packed(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out,
+                                    disco_c32* Rss, disco_c32* Rnn, int reuse, disco_stream s);
 
 #define DISCO_PK_SELFTEST_OPS 23
 int disco_selftest_pk(disco_ctx* ctx, const disco_c32* a, const disco_c32* b, const disco_c32* c, int64_t n,

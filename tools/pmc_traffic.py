@@ -66,7 +66,7 @@ for k, v in raw.items():
         ent['hbm_bytes_per_launch'] = 2 * f * 1024 + w * 1024
     stage = next((s for p, s in STAGE_OF.items() if name.startswith(p)), name)
     # bench.py looks the dominant stage up by ITS name: map kernels to the stage they serve in the profiled configuration
-    if stage == 'stft_cov1' and ', false>' in name:
+    if stage == 'stft_cov1' and re.match(r'k_stft_cov<\d+, \d+, false', name):     # STORE = false (the 3rd argument; a 4th, the layout, may follow)
         stage = 'stft_cov1_nostore'
     if stage in ('solve', 'solve_thread'):
         stage = 'solve1' if (stage == 'solve_thread' or '<4,' in name or '<8,' in name) else 'solve2'
