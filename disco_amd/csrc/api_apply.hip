@@ -20,63 +20,39 @@ extern "C" int disco_apply(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
     const long long TF = (long long)ctx->T * ctx->F;
     int bpn = (int)std::min<long long>((TF + 255) / 256, 64);
     while ((long long)bpn * G > 0x7fffffffLL && bpn > 1) bpn >>= 1;
-    const dim3 grid((unsigned)(G * bpn)), block(256);
-    bool launched = false;
-#define X_(M_, KR_)                                                                                                  \
-    if (!launched && M == M_ && KR == KR_) {                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply<M_, KR_>), grid, block, 0, (hipStream_t)s, (const c32*)X,         \
-                           (const c32*)Z, (const c32*)w, (c32*)out, c.nodes, ctx->T, ctx->F, conj_w, bpn, ctx->Kl,   \
-                           ctx->k0, ctx->zblk, (long long)c.rooms);                                                                                 \
-        launched = true;                                                                                             \
-    }
-    DISCO_FOR_MKR(X_)
-#undef X_
-    if (!launched) {
-        const int tiles = (ctx->F + 63) / 64;
-        const long long Gg = (long long)ctx->geom_rooms * ctx->Kl;
+    const hipStream_t st = (hipStream_t)s;
+    const c32 *Xc = (const c32*)X, *Zc = (const c32*)Z, *wc = (const c32*)w;
+    const bool flat = for_mkr(M, KR, [&](auto m, auto kr) {            // P <= 8: flat over (t, f)
+        constexpr int M_ = decltype(m)::value, KR_ = decltype(kr)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply<M_, KR_>), dim3((unsigned)(G * bpn)), dim3(256), 0, st, Xc, Zc, wc, (c32*)out, c.nodes, ctx->T, ctx->F,
+                           conj_w, bpn, ctx->Kl, ctx->k0, ctx->zblk, (long long)c.rooms);
+    });
+    if (flat) return check_launch(ctx, "k_apply");
+    const int tiles = (ctx->F + 63) / 64;
+    const long long Gg = (long long)ctx->geom_rooms * ctx->Kl;
 #ifndef DISCO_APPLY_ITEMS
 #define DISCO_APPLY_ITEMS 131072            // workgroups aimed at: more, shorter frame runs keep the nodes of a room in step (their remote rows meet in L2): 3 -> 10 chunks at C5 read 21.7 instead of 25.5 GB (profiles/r03_r_*)
 #endif
-        int t_chunks = (int)std::min<long long>(std::max<long long>(1, (DISCO_APPLY_ITEMS + Gg * tiles - 1) / (Gg * tiles)), std::max(1, ctx->T / 8));
-        while (G * tiles * t_chunks > 0x7ffffff0LL && t_chunks > 1) t_chunks >>= 1;
-        const long long items_m = G * tiles * t_chunks;
-        const dim3 grid_m((unsigned)((items_m + DISCO_APPLY_XCD - 1) / DISCO_APPLY_XCD * DISCO_APPLY_XCD));      // ids are dealt over the XCDs
-        if ((M == 4 || M == 8) && KR >= 1 && KR <= 15) {        // contiguous granule loads through a wave-private LDS tile (k_apply_mq)
-            const int krt = KR <= 1 ? 1 : (KR <= 3 ? 3 : (KR <= 7 ? 7 : 15));
-#define Q_(M_, KRT_)                                                                                                                  \
-    if (M == M_ && krt == KRT_)                                                                                                       \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_mq<M_, KRT_>), grid_m, dim3(64), 0, (hipStream_t)s, (const c32*)X, (const c32*)Z,  \
-                           (const c32*)w, (c32*)out, KR, c.nodes, ctx->T, ctx->F, conj_w, tiles, t_chunks, ctx->Kl, ctx->k0, ctx->zblk, \
-                           (long long)c.rooms);
-            Q_(4, 1) Q_(4, 3) Q_(4, 7) Q_(4, 15) Q_(8, 1) Q_(8, 3) Q_(8, 7) Q_(8, 15)
-#undef Q_
-            return check_launch(ctx, "k_apply_mq");
-        }
-        if (KR > 15) {                              // wide networks (P > 16 with more than 15 remote rows)
-            switch (M) {
-#define C_(M_)                                                                                                          \
-    case M_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_m<M_, 31>), grid_m, dim3(64), 0, (hipStream_t)s, (const c32*)X, (const c32*)Z, \
-                           (const c32*)w, (c32*)out, KR, c.nodes, ctx->T, ctx->F, conj_w, tiles, t_chunks, ctx->Kl, ctx->k0, ctx->zblk, \
-                           (long long)c.rooms);                                                                    \
-        break;
-                C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8)
-#undef C_
-            }
-            return check_launch(ctx, "k_apply_m");
-        }
-        switch (M) {
-#define C_(M_)                                                                                                          \
-    case M_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_m<M_>), grid_m, dim3(64), 0, (hipStream_t)s, (const c32*)X, (const c32*)Z, \
-                           (const c32*)w, (c32*)out, KR, c.nodes, ctx->T, ctx->F, conj_w, tiles, t_chunks, ctx->Kl, ctx->k0, ctx->zblk, \
-                           (long long)c.rooms);                                                                    \
-        break;
-            C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8)
-#undef C_
-            default: return fail(ctx, DISCO_E_UNSUPPORTED, "disco_apply: more than 8 mics per node");
-        }
+    int t_chunks = (int)std::min<long long>(std::max<long long>(1, (DISCO_APPLY_ITEMS + Gg * tiles - 1) / (Gg * tiles)), std::max(1, ctx->T / 8));
+    while (G * tiles * t_chunks > 0x7ffffff0LL && t_chunks > 1) t_chunks >>= 1;
+    const long long items_m = G * tiles * t_chunks;
+    const dim3 grid_m((unsigned)((items_m + DISCO_APPLY_XCD - 1) / DISCO_APPLY_XCD * DISCO_APPLY_XCD));      // ids are dealt over the XCDs
+    // the three wave-per-tile kernels take the same arguments
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid_m, dim3(64), 0, st, Xc, Zc, wc, (c32*)out, KR, c.nodes, ctx->T, ctx->F, conj_w, tiles, t_chunks, ctx->Kl,
+                           ctx->k0, ctx->zblk, (long long)c.rooms);
+    };
+    if ((M == 4 || M == 8) && KR >= 1 && KR <= 15) {        // contiguous granule loads through a wave-private LDS tile (k_apply_mq)
+        const int krt = KR <= 1 ? 1 : (KR <= 3 ? 3 : (KR <= 7 ? 7 : 15));
+        for_apply_mq(M, krt, [&](auto m, auto k) { launch(k_apply_mq<decltype(m)::value, decltype(k)::value>); });
+        return check_launch(ctx, "k_apply_mq");
     }
+    if (KR > 15) {                              // wide networks (P > 16 with more than 15 remote rows)
+        for_int<1, 8>(M, [&](auto m) { launch(k_apply_m<decltype(m)::value, 31>); });
+        return check_launch(ctx, "k_apply_m");
+    }
+    if (!for_int<1, 8>(M, [&](auto m) { launch(k_apply_m<decltype(m)::value>); }))
+        return fail(ctx, DISCO_E_UNSUPPORTED, "disco_apply: more than 8 mics per node");
     return check_launch(ctx, "k_apply");
 }
 

@@ -3,33 +3,22 @@
 // shard's step 2 on gathered z (disco_apply_istft_fused)
 #include "host.h"
 #include "k_fused.h"
-#include "room_launch.h"
+#include "room_launch.h"      // (nothing of it is used here; it brings k_room.h's static self-test kernel into this unit's code object, as ever)
 
 using namespace disco;
 using namespace disco_host;
 
-// shapes the one-pass kernel is built for: the wide (M, K) shapes of the room pass (the whole-path calls end in it) and the narrow 4-mic shapes
-// a NODE SHARD needs it for (with all nodes of a room on the GPU those keep z on chip: k_step2_apply_istft; a shard gets z from the all-gather)
-#define DISCO_FOR_WIDE_ISTFT(X_) DISCO_FOR_ROOM(X_) X_(4, 4) X_(4, 3) X_(4, 2)
-
 namespace disco_host {
+// shapes the one-pass kernel is built for (dispatch.h: DISCO_FOR_WIDE_ISTFT), both FFT sizes
 static bool wide_istft_shape(const disco_cfg& c) {
-    if (c.n_fft != 512 && c.n_fft != 1024) return false;
-#define X_(M_, K_) if (c.mics == M_ && c.nodes == K_) return true;
-    DISCO_FOR_WIDE_ISTFT(X_)
-#undef X_
-    return false;
+    return (c.n_fft == 512 || c.n_fft == 1024) && for_wide_istft(c.mics, c.nodes, [](auto, auto) {});
 }
 // does a whole-path call of this context end in the one-pass kernel?  512 / 1024-point STFT, the wide (M, K) shapes of the room pass, every node of
 // a room on this GPU
 bool apply_istft_wide_ok(const disco_ctx* ctx) {
     const disco_cfg& c = ctx->cfg;
     if (ctx->opt[DISCO_OPT_FUSE_WIDE_ISTFT] == 0 || sharded(ctx)) return false;
-    if (c.n_fft != 512 && c.n_fft != 1024) return false;
-#define X_(M_, K_) if (c.mics == M_ && c.nodes == K_) return true;
-    DISCO_FOR_ROOM(X_)
-#undef X_
-    return false;
+    return (c.n_fft == 512 || c.n_fft == 1024) && for_room(c.mics, c.nodes, [](auto, auto) {});
 }
 
 // out [R][Kl][L] = iSTFT(w^H [X; z]) (tango.py:445 + 528); yf [R][Kl][T][F] or NULL.  Honours the node shard and the z-block layout.
@@ -65,20 +54,12 @@ int apply_istft_wide(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, con
     a.k0 = ctx->k0;
     a.zblk = ctx->zblk;
     a.lens = ctx->d_lens;
-    bool launched = false;
-#define X_(M_, K_)                                                                                                                          \
-    if (!launched && c.mics == M_ && K == K_) {                                                                                             \
-        launched = true;                                                                                                                    \
-        if (c.n_fft == 1024)                                                                                                                \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_istft_wide<1024, M_, K_ - 1>), dim3((unsigned)nblk), dim3(768), 0, (hipStream_t)s, a,   \
-                               ctx->d_win, ctx->d_tw);                                                                                      \
-        else                                                                                                                                \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_istft_wide<512, M_, K_ - 1>), dim3((unsigned)nblk), dim3(384), 0, (hipStream_t)s, a,    \
-                               ctx->d_win, ctx->d_tw);                                                                                      \
-    }
-    DISCO_FOR_WIDE_ISTFT(X_)
-#undef X_
-    if (!launched) return DISCO_E_UNSUPPORTED;
+    const bool found = for_wide_istft(c.mics, K, [&](auto m, auto k) { with_bool(c.n_fft == 1024, [&](auto n1024) {
+        constexpr int N = decltype(n1024)::value ? 1024 : 512, M_ = decltype(m)::value, KR_ = decltype(k)::value - 1;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_apply_istft_wide<N, M_, KR_>), dim3((unsigned)nblk), dim3(64 * 3 * WV), 0, (hipStream_t)s, a, ctx->d_win,
+                           ctx->d_tw);
+    }); });
+    if (!found) return DISCO_E_UNSUPPORTED;
     return check_launch(ctx, "k_apply_istft_wide");
 }
 }  // namespace disco_host

@@ -79,17 +79,17 @@ static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* ma
         return fail(ctx, DISCO_E_UNSUPPORTED, m);
     }
     const CovArgs a = cov_args(ctx, X, mask, Zs, Zn, part, chunks, mask_remote);
-    if (Zs == Zn)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<true>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<false>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
+    with_bool(Zs == Zn, [&](auto samez) {
+        constexpr bool SAMEZ = decltype(samez)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<SAMEZ>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
+    });
     partials_commit(ctx, chunks, P, false);
     return check_launch(ctx, "k_cov_wide");
 }
 
-// (M, KR) shapes of the block-partitioned kernels k_cov_split / k_cov_split_lds (api_cov_split.hip)
+// the block-partitioned kernels k_cov_split_lds / k_cov_loc_f64 (api_cov_split.hip); false: (M, KR) is not one of their shapes
 bool cov_split_shape(int M, int KR);
-bool launch_cov_split_shape(int M, int KR, bool skiploc, int sub, unsigned nblk, hipStream_t st, const disco::CovArgs& a);
+bool launch_cov_split_shape(int M, int KR, bool skiploc, unsigned nblk, hipStream_t st, const disco::CovArgs& a);
 
 // skiploc (step 2 only, internal): where the step-1 partial sums of THIS X with THIS mask are still kept (step1_held), the leading
 // M x M block is neither accumulated nor written, the partial sums go to the tail block and the solver assembles the pencil from
@@ -110,48 +110,35 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
     const bool same = (Zs == Zn);
     const bool split = (KR == 0 || (P > 8 && same && mask_remote && (ctx->F - 1) % 64 == 0)) && cov_split_shape(M, KR);
     // step-1 shapes of the split kernels (KR = 0, M >= 7): float64 accumulators, every frame chunk leaves a (hi, lo) PAIR of partial blocks
-    const int sub = (split && KR == 0) ? 64 : 1;
-    if (sub == 64) chunks = cov1_f64_chunks(ctx);
-    const int blocks = sub == 64 ? 2 * chunks : chunks;
+    const bool f64 = split && KR == 0;
+    if (f64) chunks = cov1_f64_chunks(ctx);
+    const int blocks = f64 ? 2 * chunks : chunks;
     const size_t need = (size_t)G * blocks * ctx->F * NP * sizeof(float4);
     skiploc = skiploc && split && KR > 0 && step1_held(ctx, X, mask);
     int rc = 0;
     float4* part = partials_begin(ctx, need, skiploc, &rc);
     if (rc) return rc;
     const CovArgs a = cov_args(ctx, X, mask, Zs, Zn, part, chunks, mask_remote);
-    const dim3 grid((unsigned)(G * chunks)), block((unsigned)(ctx->F - 1 + 64));
-    bool launched = false;
-    if (split) {                // 9 <= P <= 16, one vector for both statistics: one block of pairs per wave
-        const int tiles = (ctx->F - 1 + 63) / 64;
-        const long long nblk = G * (tiles + 1) * chunks;
+    const hipStream_t st = (hipStream_t)s;
+    // one workgroup per (node, bin tile | Nyquist, chunk): the split kernels and k_cov_big
+    const long long nblk = G * ((ctx->F - 1 + 63) / 64 + 1) * chunks;
+    const bool mkr = !split && for_mkr(M, KR, [&](auto m, auto kr) {          // P <= 8: one thread per bin holds the whole triangle
+        with_bool(c.n_fft == 512, [&](auto n512) { with_bool(KR == 0 || same, [&](auto samez) {
+            constexpr int M_ = decltype(m)::value, KR_ = decltype(kr)::value, NT = decltype(n512)::value ? 320 : 576;
+            constexpr bool SAMEZ = decltype(samez)::value;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<M_, KR_, SAMEZ, NT>), dim3((unsigned)(G * chunks)),
+                               dim3((unsigned)(ctx->F - 1 + 64)), 0, st, a);
+        }); });
+    });
+    if (!mkr) {                 // 9 <= P <= 16 (and the step-1 shapes M >= 7)
         if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: batch too large");
-        launched = launch_cov_split_shape(M, KR, skiploc, sub, (unsigned)nblk, (hipStream_t)s, a);
-    }
-#define X_(M_, KR_)                                                                                                  \
-    if (!launched && M == M_ && KR == KR_) {                                                                         \
-        if (c.n_fft == 512) {                                                                                        \
-            if (KR_ == 0 || same)                                                                                    \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<M_, KR_, true, 320>), grid, block, 0, (hipStream_t)s, a);   \
-            else                                                                                                     \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<M_, KR_, false, 320>), grid, block, 0, (hipStream_t)s, a);  \
-        } else {                                                                                                     \
-            if (KR_ == 0 || same)                                                                                    \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<M_, KR_, true, 576>), grid, block, 0, (hipStream_t)s, a);   \
-            else                                                                                                     \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<M_, KR_, false, 576>), grid, block, 0, (hipStream_t)s, a);  \
-        }                                                                                                            \
-        launched = true;                                                                                             \
-    }
-    DISCO_FOR_MKR(X_)
-#undef X_
-    if (!launched) {            // 9 <= P <= 16: pairs split over the waves of a workgroup
-        const int tiles = (ctx->F - 1 + 63) / 64;
-        const long long nblk = G * (tiles + 1) * chunks;
-        if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: batch too large");
-        if (KR == 0 || same)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_big<true>), dim3((unsigned)nblk), dim3(64 * CB_S), 0, (hipStream_t)s, a, M, KR);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_big<false>), dim3((unsigned)nblk), dim3(64 * CB_S), 0, (hipStream_t)s, a, M, KR);
+        if (split)              // one vector for both statistics: one block of pairs per wave
+            launch_cov_split_shape(M, KR, skiploc, (unsigned)nblk, st, a);
+        else                    // pairs split over the waves of a workgroup
+            with_bool(KR == 0 || same, [&](auto samez) {
+                constexpr bool SAMEZ = decltype(samez)::value;
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_big<SAMEZ>), dim3((unsigned)nblk), dim3(64 * CB_S), 0, st, a, M, KR);
+            });
     }
     partials_commit(ctx, blocks, P, skiploc);
     // step-1 sums (P == M, all nodes here) can be re-used by a step 2 on the same mask

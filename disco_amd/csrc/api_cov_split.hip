@@ -4,14 +4,12 @@
 
 namespace disco_host {
 bool cov_split_shape(int M, int KR) {
-#define X_(M_, KR_) if (M == M_ && KR == KR_) return true;
-    DISCO_FOR_SPLIT_M8(X_) DISCO_FOR_SPLIT_M4(X_) DISCO_FOR_SPLIT_M2(X_)
-#undef X_
-    return false;
+    const auto is_shape = [](auto, auto) {};
+    return for_split_m8(M, KR, is_shape) || for_split_m4(M, KR, is_shape) || for_split_m2(M, KR, is_shape);
 }
 
-bool launch_cov_split_shape(int M, int KR, bool skiploc, int sub, unsigned nblk, hipStream_t st, const CovArgs& a) {
-    return launch_cov_split_m8(M, KR, skiploc, sub, nblk, st, a) || launch_cov_split_m4(M, KR, skiploc, sub, nblk, st, a) ||
-           launch_cov_split_m2(M, KR, skiploc, sub, nblk, st, a);
+bool launch_cov_split_shape(int M, int KR, bool skiploc, unsigned nblk, hipStream_t st, const CovArgs& a) {
+    return launch_cov_split_m8(M, KR, skiploc, nblk, st, a) || launch_cov_split_m4(M, KR, skiploc, nblk, st, a) ||
+           launch_cov_split_m2(M, KR, skiploc, nblk, st, a);
 }
 }  // namespace disco_host

@@ -2,5 +2,7 @@
 #include "cov_split_launch.h"
 
 namespace disco_host {
-DISCO_DEFINE_SPLIT_LAUNCHER(launch_cov_split_m2, DISCO_FOR_SPLIT_M2)
+bool launch_cov_split_m2(int M, int KR, bool skiploc, unsigned nblk, hipStream_t st, const CovArgs& a) {
+    return for_split_m2(M, KR, [&](auto m, auto kr) { launch_cov_split<decltype(m)::value, decltype(kr)::value>(skiploc, nblk, st, a); });
+}
 }  // namespace disco_host

@@ -30,10 +30,6 @@ extern "C" int disco_gevd_mwf(disco_ctx* ctx, const disco_c32* Rxx, const disco_
     const c32* a = (const c32*)Rxx;
     const c32* b = (const c32*)Rnn;
     hipStream_t st = (hipStream_t)s;
-    switch (P) {
-#define C_(P_) case P_: launch_gevd_full<P_>(a, b, n_prob, r, (double)mu, (c32*)w, (c32*)t1, st); break;
-        C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9) C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
-#undef C_
-    }
+    for_int<1, 16>(P, [&](auto p) { launch_gevd_full<decltype(p)::value>(a, b, n_prob, r, (double)mu, (c32*)w, (c32*)t1, st); });
     return check_launch(ctx, "k_gevd_full");
 }

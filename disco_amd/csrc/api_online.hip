@@ -49,39 +49,24 @@ static int online_mwf_walk(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
     a.zblk = ctx->zblk;
     a.R = c.rooms;
     hipStream_t st = (hipStream_t)s;
-    switch (P) {
-#define C_(P_)                                                                                                          \
-    case P_: {                          /* one thread per (room, node, bin) */                                          \
-        constexpr int SOLVE_SMALL_THREADS = solve_small_threads<P_>();                                                  \
-        const long long grid = (a.n_prob + SOLVE_SMALL_THREADS - 1) / SOLVE_SMALL_THREADS;                              \
-        if (P_ > 1 && ctx->opt[DISCO_OPT_ONLINE_SQ32] != 0)     /* the squarings in packed float32 (k_solve_small.h) */           \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_online_mwf_thread<P_, (P_ > 1)>), dim3((unsigned)grid), dim3(SOLVE_SMALL_THREADS), 0, st, a); \
-        else                                                                                                            \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_online_mwf_thread<P_, false>), dim3((unsigned)grid), dim3(SOLVE_SMALL_THREADS), 0, st, a); \
-    } break;
-        C_(1) C_(2) C_(3) C_(4)
-        default: break;
-    }
-    // 5 <= P <= 7, option "solve_thread": one thread per problem as well (the float64 solve in the registers of one thread, AGPRs as its
-    // second register file: k_solve_small.h)
-    if (P >= 5 && P <= 7 && ctx->opt[DISCO_OPT_SOLVE_THREAD] != 0) {
-        switch (P) {
-            C_(5) C_(6) C_(7)
-        }
+    // P <= 4, and 5 <= P <= 7 under option "solve_thread": one thread per (room, node, bin) (the float64 solve in the registers of one thread,
+    // AGPRs as its second register file: k_solve_small.h)
+    if (P <= 4 || (P <= 7 && ctx->opt[DISCO_OPT_SOLVE_THREAD] != 0)) {
+        for_int<1, 7>(P, [&](auto p) { with_bool(P > 1 && ctx->opt[DISCO_OPT_ONLINE_SQ32] != 0, [&](auto sq32) {      // the squarings in packed float32
+            constexpr int P_ = decltype(p)::value, THREADS = solve_small_threads<P_>();
+            constexpr bool SQ32 = P_ > 1 && decltype(sq32)::value;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_online_mwf_thread<P_, SQ32>), dim3((unsigned)((a.n_prob + THREADS - 1) / THREADS)),
+                               dim3(THREADS), 0, st, a);
+        }); });
         return check_launch(ctx, "k_online_mwf_thread");
     }
-    if (P <= 4) return check_launch(ctx, "k_online_mwf_thread");
-    switch (P) {
-#undef C_
-#define C_(P_)                                                                                                          \
-    case P_: {                          /* a group of 8 / 16 lanes per (room, node, bin) */                             \
-        const long long grid = (a.n_prob + SolveGeom<P_>::PROBS - 1) / SolveGeom<P_>::PROBS;                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_online_mwf<P_>), dim3((unsigned)grid), dim3(SolveGeom<P_>::THREADS), 0, st, a); \
-    } break;
-        C_(5) C_(6) C_(7) C_(8) C_(9) C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
-#undef C_
-        default: return fail(ctx, DISCO_E_UNSUPPORTED, "disco_online_mwf: no kernel for this P");
-    }
+    const bool found = for_int<5, 16>(P, [&](auto p) {         // a group of 8 / 16 lanes per (room, node, bin)
+        constexpr int P_ = decltype(p)::value;
+        using Geom = SolveGeom<P_>;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_online_mwf<P_>), dim3((unsigned)((a.n_prob + Geom::PROBS - 1) / Geom::PROBS)), dim3(Geom::THREADS), 0,
+                           st, a);
+    });
+    if (!found) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_online_mwf: no kernel for this P");
     return check_launch(ctx, "k_online_mwf");
 }
 

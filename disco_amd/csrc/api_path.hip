@@ -223,7 +223,9 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
     if (c.nodes == 1 && same_mask && !z_y && !yf && c.n_fft == 512 && M <= 4) {
         // single node, enhanced output only (config C2): nothing is materialised -- one pass over the samples for the
         // statistics, one for filter + iSTFT with the spectra recomputed (get_z_signals.py:274-315 + tango.py:528)
-        st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, nullptr, s, false); }});
+        StftCovOpts no_spectra;
+        no_spectra.store = false;
+        st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, nullptr, s, no_spectra); }});
         st.push_back({"solve1", true, solve_pending(w)});
         st.push_back({"stft_apply_istft", false, [=](disco_stream s) { return stft_apply_istft(ctx, y, w, out, s); }});
         return;
@@ -235,24 +237,23 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
     // ... and on that branch X never leaves the workspace, so its rows may take the packed layout ("packed_x", k_stft.h k_stft_cov: [T][F - 1][M],
     // the Nyquist bin in the DC slot): every wave load and store of the three passes over X then covers whole 128-byte lines.  The slot of
     // X in the workspace keeps its size (the packed array is 1 / F smaller), so one workspace serves both values of the option.
-    const bool packed = !x_zeros && ctx->opt[DISCO_OPT_PACKED_X] != 0;
-    st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, X, s, true, x_zeros, packed); }});
+    const XLayout layout = !x_zeros && ctx->opt[DISCO_OPT_PACKED_X] != 0 ? XLayout::Packed : XLayout::Public;
+    StftCovOpts step1;
+    step1.zero_beyond = x_zeros;
+    step1.layout = layout;
+    st.push_back({nullptr, false, [=](disco_stream s) { return stft_cov_partials(ctx, y, mask_z, X, s, step1); }});
     st.push_back({"solve1", true, solve_pending(w)});
 
     if (fused_route(ctx)) {
         // same mask array in both steps (oracle masks; a DNN mask re-used, tango.py:388-389): the leading M x M block of the
         // step-2 covariances IS the step-1 covariance still held as partial sums -> not recomputed
         st.push_back({"step2_cov", false, [=](disco_stream s) {
-            if (step1_held(ctx, X, mask_w)) {
-                if (packed) return step2_cov_partials(ctx, X, mask_w, w, z_y, s, true, true);
-                return disco_step2_cov_fused_reuse(ctx, X, mask_w, w, z_y, s);
-            }
-            return step2_cov_partials(ctx, X, mask_w, w, z_y, s, false, packed);
+            return step2_cov_partials(ctx, X, mask_w, w, z_y, s, step1_held(ctx, X, mask_w) ? LeadBlock::Step1 : LeadBlock::Accumulate, layout);
         }});
         st.push_back({"solve2", true, solve_pending(w2)});
         if (!yf && c.n_fft == 512) {   // yf not asked for: filter + iSTFT in one pass, yf stays on chip (shapes the kernel takes)
             if (step2_apply_istft_ok(ctx)) {
-                st.push_back({"step2_apply_istft", false, [=](disco_stream s) { return step2_apply_istft(ctx, X, w, w2, out, s, packed); }});
+                st.push_back({"step2_apply_istft", false, [=](disco_stream s) { return step2_apply_istft(ctx, X, w, w2, out, s, layout); }});
                 return;
             }
         }

@@ -11,10 +11,7 @@ namespace disco_host {
 bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask) {
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics, K = c.nodes;
-    bool shape = false;
-#define X_(M_, K_) if (M == M_ && K == K_) shape = true;
-    DISCO_FOR_ROOM(X_)
-#undef X_
+    const bool shape = for_room(M, K, [](auto, auto) {});
     const bool want = ctx->opt[DISCO_OPT_ROOM_COV] != 0;
     if (!want || !shape || M + K - 1 <= 8 || sharded(ctx) || !X || !mask) return false;
     if (!step1_held(ctx, X, mask)) return false;                                             // the leading M x M block must be step 1's

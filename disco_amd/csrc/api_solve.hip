@@ -59,11 +59,9 @@ static int solve_dispatch(disco_ctx* ctx, const SolveSrc& src, int64_t n_prob, i
         launch_solve_dpp(P, src, n_prob, (double)mu, (c32*)w, (c32*)t1, st);
         return check_launch(ctx, "k_gevd_mwf_r1_dpp");
     }
-    switch (P) {
-#define C_(P_) case P_: launch_solve<P_>(src, n_prob, (double)mu, (c32*)w, (c32*)t1, st, ctx->opt[DISCO_OPT_SOLVE_THREAD] != 0); break;
-        C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9) C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
-#undef C_
-    }
+    for_int<1, 16>(P, [&](auto p) {
+        launch_solve<decltype(p)::value>(src, n_prob, (double)mu, (c32*)w, (c32*)t1, st, ctx->opt[DISCO_OPT_SOLVE_THREAD] != 0);
+    });
     return check_launch(ctx, "k_gevd_mwf_r1");
 }
 

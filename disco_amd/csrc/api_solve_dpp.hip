@@ -19,11 +19,7 @@ static void launch(const SolveSrc& src, long long n_prob, double mu, c32* w, c32
 }
 
 void launch_solve_dpp(int P, const SolveSrc& src, long long n_prob, double mu, c32* w, c32* t1, hipStream_t s) {
-    switch (P) {
-#define C_(P_) case P_: launch<P_>(src, n_prob, mu, w, t1, s); break;
-        C_(9) C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
-#undef C_
-    }
+    for_int<9, 16>(P, [&](auto p) { launch<decltype(p)::value>(src, n_prob, mu, w, t1, s); });
 }
 
 }  // namespace disco_host

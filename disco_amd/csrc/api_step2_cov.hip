@@ -1,24 +1,10 @@
 // libdisco_hip.so -- host side of the C ABI declared in include/disco_hip.h (gfx950 only): step 2 with the z exchange on chip: covariances
-#include "host.h"
-#include "k_fused.h"
+#include "step2_launch.h"
 
 using namespace disco;
 using namespace disco_host;
 
-// ---------------------------------------------------------------------------------------------------------
 // step 2 with the in-register z exchange
-// ---------------------------------------------------------------------------------------------------------
-template <int M, int K>
-static bool launch_step2_cov_packed(const Step2Args& a, bool skiploc, dim3 grid, hipStream_t st) {
-    if constexpr (K >= 2) {
-        if (skiploc) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M, K, true, true>), grid, dim3(64 * K), 0, st, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M, K, false, true>), grid, dim3(64 * K), 0, st, a);
-        return true;
-    } else {
-        return false;
-    }
-}
-
 namespace disco_host {
 int step2_chunks(const disco_ctx* ctx, int tiles_plus_1) {
     const long long base = (long long)ctx->geom_rooms * tiles_plus_1;
@@ -30,16 +16,16 @@ int step2_chunks(const disco_ctx* ctx, int tiles_plus_1) {
     return (int)c;
 }
 
-// skiploc: the caller has checked that the step-1 partial sums of THIS X with THIS mask are still kept (step1_held); the leading
-// M x M block is then neither accumulated nor written and the step-2 partials go to the tail block.
-// packed: X is in the packed workspace layout [R][K][T][F - 1][M] (k_stft.h; K >= 2, 512 points) -- the same z and partial sums.
-int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
-                       disco_c32* z_out, disco_stream s, bool skiploc, bool packed) {
+// lead, layout: host.h.  The packed layout is that of the shapes the fused route of the whole path takes (K >= 2, 512 points) -- the same z and
+// partial sums.
+int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out, disco_stream s,
+                       LeadBlock lead, XLayout layout) {
     if (!X || !mask_w || !w_loc) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: null argument");
     if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "fused kernels need every node of a room on this GPU (node shard active)");
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics, K = c.nodes, P = M + K - 1;
     if (P > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: M + K - 1 > 8 not supported yet");
+    const bool skiploc = lead == LeadBlock::Step1, packed = layout == XLayout::Packed;
     const int tiles = (ctx->F - 1) / 64;
     const int chunks = step2_chunks(ctx, tiles + 1);
     const long long G = (long long)c.rooms * K;
@@ -48,42 +34,17 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     int rc = 0;
     float4* part = partials_begin(ctx, need, skiploc, &rc);
     if (rc) return rc;
-    Step2Args a;
-    a.X = (const c32*)X;
-    a.mask = mask_w;
-    a.w_loc = (const c32*)w_loc;
-    a.w_glo = nullptr;
-    a.z_out = (c32*)z_out;
-    a.yf = nullptr;
-    a.part = part;
-    a.K = K;
-    a.T = ctx->T;
-    a.F = ctx->F;
-    a.chunks = chunks;
-    a.lens = ctx->d_lens;
+    const Step2Args a = step2_args(ctx, X, mask_w, w_loc, nullptr, z_out, nullptr, part, chunks);
     const long long nblk = (long long)c.rooms * (tiles + 1) * chunks;
     if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: batch too large");
-    bool launched = false;
     if (packed && (K < 2 || c.n_fft != 512)) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: the packed layout needs K >= 2 and n_fft = 512");
-    // the packed layout: the shapes the fused route of the whole path takes (K >= 2)
-#define X_(M_, KR_)                                                                                                  \
-    if (!launched && packed && M == M_ && K == KR_ + 1)                                                              \
-        launched = launch_step2_cov_packed<M_, KR_ + 1>(a, skiploc, dim3((unsigned)nblk), (hipStream_t)s);
-    DISCO_FOR_MKR(X_)
-#undef X_
-#define X_(M_, KR_)                                                                                                  \
-    if (!launched && M == M_ && K == KR_ + 1) {                                                                      \
-        if (skiploc)                                                                                                 \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M_, KR_ + 1, true>), dim3((unsigned)nblk),          \
-                               dim3(64 * (KR_ + 1)), 0, (hipStream_t)s, a);                                          \
-        else                                                                                                         \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M_, KR_ + 1, false>), dim3((unsigned)nblk),         \
-                               dim3(64 * (KR_ + 1)), 0, (hipStream_t)s, a);                                          \
-        launched = true;                                                                                             \
-    }
-    DISCO_FOR_MKR(X_)
-#undef X_
-    if (!launched) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: unsupported (M, K) combination");
+    const bool found = for_mkr(M, K - 1, [&](auto m, auto kr) { with_bool(skiploc, [&](auto skip) { with_bool(packed, [&](auto pack) {
+        constexpr int M_ = decltype(m)::value, K_ = decltype(kr)::value + 1;
+        constexpr bool SKIPLOC = decltype(skip)::value, PACK = decltype(pack)::value;
+        if constexpr (!PACK || K_ >= 2)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M_, K_, SKIPLOC, PACK>), dim3((unsigned)nblk), dim3(64 * K_), 0, (hipStream_t)s, a);
+    }); }); });
+    if (!found) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: unsupported (M, K) combination");
     partials_commit(ctx, chunks, P, skiploc);
     return check_launch(ctx, "k_step2_cov_fused");
 }
@@ -97,13 +58,13 @@ extern "C" int disco_step2_cov_fused_reuse(disco_ctx* ctx, const disco_c32* X, c
         return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused_reuse: no step-1 partial sums of disco_stft_cov_fused are held by this context");
     if (!step1_held(ctx, X, mask_w))
         return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused_reuse: X / mask_w are not the arrays the held step-1 partial sums were computed from");
-    return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, true);
+    return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Step1, XLayout::Public);
 }
 extern "C" int disco_step2_cov_fused(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
                                      disco_c32* z_out, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: Rss and Rnn must both be given or both be NULL");
-    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s);
+    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Accumulate, XLayout::Public);
     if (rc || !Rss) return rc;
     return cov_finalize(ctx, Rss, Rnn, s);
 }
@@ -117,9 +78,9 @@ extern "C" int disco_selftest_step2_cov_packed(disco_ctx* ctx, const disco_c32* 
     if (reuse) {
         if (!step1_any(ctx) || ctx->cfg.nodes < 2 || ctx->Kl != ctx->cfg.nodes || !step1_held(ctx, X, mask_w))
             return fail(ctx, DISCO_E_ARG, "disco_selftest_step2_cov_packed: no step-1 partial sums of X / mask_w are held by this context");
-        return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, true, true);
+        return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Step1, XLayout::Packed);
     }
-    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, false, true);
+    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Accumulate, XLayout::Packed);
     if (rc || !Rss) return rc;
     return cov_finalize(ctx, Rss, Rnn, s);
 }

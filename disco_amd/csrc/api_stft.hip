@@ -20,15 +20,10 @@ static bool launch_stft(int chp, dim3 grid, hipStream_t st, const float* x, c32*
                            runs, lens, spr);
         return true;
     }
-    switch (chp) {
-#define C_(P_)                                                                                                          \
-    case P_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft<N, P_>), grid, block, 0, st, x, X, win, tw, chans, L, T, pad_mode, runs, n_items, lens, spr); \
-        return true;
-        C_(1) C_(2)
-#undef C_
-    }
-    return false;
+    return for_int<1, 2>(chp, [&](auto p) {
+        constexpr int CHP = decltype(p)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft<N, CHP>), grid, block, 0, st, x, X, win, tw, chans, L, T, pad_mode, runs, n_items, lens, spr);
+    });
 }
 
 // the transform of signals of ANY length L (T = 1 + L / hop frames) with this context's window, FFT size and padding: disco_stft passes the
@@ -55,9 +50,10 @@ int stft_any(disco_ctx* ctx, const float* x, int64_t n_sig, int chans, disco_c32
     const disco_cfg& c = ctx->cfg;
     const dim3 grid((unsigned)stft_blocks(n_items));
     const int chp = (chans + 1) / 2;
-    const bool ok = c.n_fft == 512
-        ? launch_stft<512>(chp, grid, (hipStream_t)s, x, (c32*)X, ctx->d_win, ctx->d_tw, chans, L, T, c.pad_mode, runs, n_items, lens, spr)
-        : launch_stft<1024>(chp, grid, (hipStream_t)s, x, (c32*)X, ctx->d_win, ctx->d_tw, chans, L, T, c.pad_mode, runs, n_items, lens, spr);
+    const bool ok = with_bool(c.n_fft == 512, [&](auto n512) {
+        return launch_stft<decltype(n512)::value ? 512 : 1024>(chp, grid, (hipStream_t)s, x, (c32*)X, ctx->d_win, ctx->d_tw, chans, L, T, c.pad_mode, runs,
+                                                                n_items, lens, spr);
+    });
     if (!ok) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft: unsupported channel count");
     return check_launch(ctx, "k_stft");
 }
@@ -88,14 +84,11 @@ extern "C" int disco_mask_oracle(disco_ctx* ctx, const float* s_ref, const float
     const float thr = powf(10.f, c.mask_bin_thr_db / 10.f);                 // math_utils.py db2lin (power)
     const dim3 grid((unsigned)stft_blocks(n_items));
     StageScope stage_scope_(ctx, s, "mask_oracle");
-    if (c.n_fft == 512)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mask_oracle<512>), grid, dim3(64 * STFT_WAVES), 0,
-                           (hipStream_t)s, s_ref, n_ref, mask, ctx->d_win, ctx->d_tw, c.length, ctx->T, c.pad_mode,
-                           c.mask_type, c.mask_pow, thr, runs, n_items, ctx->d_lens, spr);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mask_oracle<1024>), grid, dim3(64 * STFT_WAVES), 0,
-                           (hipStream_t)s, s_ref, n_ref, mask, ctx->d_win, ctx->d_tw, c.length, ctx->T, c.pad_mode,
-                           c.mask_type, c.mask_pow, thr, runs, n_items, ctx->d_lens, spr);
+    with_bool(c.n_fft == 512, [&](auto n512) {
+        constexpr int N = decltype(n512)::value ? 512 : 1024;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mask_oracle<N>), grid, dim3(64 * STFT_WAVES), 0, (hipStream_t)s, s_ref, n_ref,
+                           mask, ctx->d_win, ctx->d_tw, c.length, ctx->T, c.pad_mode, c.mask_type, c.mask_pow, thr, runs, n_items, ctx->d_lens, spr);
+    });
     return check_launch(ctx, "k_mask_oracle");
 }
 
@@ -122,10 +115,11 @@ int istft_any(disco_ctx* ctx, const disco_c32* Z, int64_t n_sig, float* out, int
     if (grid > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_istft: batch too large for one launch");
     const dim3 gr((unsigned)grid), bl(64 * STFT_WAVES);
     hipStream_t st = (hipStream_t)s;
-    if (c.n_fft == 512 && !solo) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_istft<512, false>), gr, bl, 0, st, (const c32*)Z, out, ctx->d_win, ctx->d_tw, L, T, bps, lens, spr);
-    else if (c.n_fft == 512) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_istft<512, true>), gr, bl, 0, st, (const c32*)Z, out, ctx->d_win, ctx->d_tw, L, T, bps, lens, spr);
-    else if (!solo) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_istft<1024, false>), gr, bl, 0, st, (const c32*)Z, out, ctx->d_win, ctx->d_tw, L, T, bps, lens, spr);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_istft<1024, true>), gr, bl, 0, st, (const c32*)Z, out, ctx->d_win, ctx->d_tw, L, T, bps, lens, spr);
+    with_bool(c.n_fft == 512, [&](auto n512) { with_bool(solo, [&](auto solo_c) {
+        constexpr int N = decltype(n512)::value ? 512 : 1024;
+        constexpr bool SOLO = decltype(solo_c)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_istft<N, SOLO>), gr, bl, 0, st, (const c32*)Z, out, ctx->d_win, ctx->d_tw, L, T, bps, lens, spr);
+    }); });
     return check_launch(ctx, "k_istft");
 }
 }  // namespace disco_host

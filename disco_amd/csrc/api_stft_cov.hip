@@ -5,37 +5,6 @@
 using namespace disco;
 using namespace disco_host;
 
-// ---------------------------------------------------------------------------------------------------------
-// STFT + step-1 covariance in one pass
-// ---------------------------------------------------------------------------------------------------------
-template <int N, bool STORE = true, bool PACK = false>
-static bool launch_stft_cov(int M, dim3 grid, hipStream_t st, const float* y, const float* mask, c32* X, float4* part,
-                            const float* win, const c32* tw, int L, int T, int pad_mode, int chunks, int runw, const int* lens, int spr,
-                            int zero_beyond) {
-    const dim3 block(64 * STFT_WAVES);
-    switch (M) {
-#define C_(M_)                                                                                                          \
-    case M_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE, PACK>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
-                           chunks, runw, lens, spr, zero_beyond);                                                       \
-        return true;
-        C_(1) C_(2) C_(3) C_(4) C_(5) C_(6)
-#undef C_
-    }
-    if constexpr (N == 512) {          // the 1024-point spectrum tile of 7-8 mics does not fit the 160 KiB LDS
-        switch (M) {
-#define C_(M_)                                                                                                          \
-    case M_:                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE, PACK>), grid, block, 0, st, y, mask, X, part, win, tw, L, T, pad_mode, \
-                           chunks, runw, lens, spr, zero_beyond);                                                       \
-        return true;
-            C_(7) C_(8)
-#undef C_
-        }
-    }
-    return false;
-}
-
 // frame chunks (= workgroups per node) of the fused STFT + covariance pass and the frames each of its waves streams: runs as long
 // as possible while leaving >= ~2048 workgroups for the chip, but NOT LONGER THAN DISCO_STFT_COV_RUN frames: a workgroup's fold sums the
 // frames of its four waves' runs in float32, and the length of that sum is what the distance of the C3 output from the float64 oracle follows
@@ -56,12 +25,9 @@ int stft_cov_chunks(const disco_ctx* ctx, int* runw_out) {
     return (ctx->T + STFT_WAVES * runw - 1) / (STFT_WAVES * runw);
 }
 
-// store = false (internal, single-node path): the spectra are not written (X may be NULL); only for shapes the fused kernel takes
-// zero_beyond = false (internal, per-room lengths): the frames of X beyond a room's clip are left unwritten -- only for a caller whose every
-// reader of X knows the lengths (the fused route of disco_tango_enhance)
-// packed = true (internal; 512 points, stored spectra): X in the packed workspace layout [G][T][F - 1][M] (k_stft.h) -- the same partial sums
-int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store, bool zero_beyond,
-                      bool packed) {
+// o: host.h (StftCovOpts)
+int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, const StftCovOpts& o) {
+    const bool store = o.store, packed = o.layout == XLayout::Packed;
     if (!y || !mask_z || (store && !X)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: null argument");
     if (packed && (!store || ctx->cfg.n_fft != 512)) return fail(ctx, DISCO_E_UNSUPPORTED, "stft_cov: the packed layout needs n_fft = 512 and stored spectra");
     // (works on a node shard too: nothing in this pass looks beyond one node -- X, masks and partial sums then hold the shard's Kl nodes per room)
@@ -86,21 +52,23 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
     float4* part = partials_begin(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4), false, &rc);
     if (rc) return rc;
     if (G * chunks > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: batch too large");
-    const dim3 grid((unsigned)(G * chunks));
-    const bool ok = !store
-        ? STAGE(ctx, s, "stft_cov1_nostore", c.n_fft == 512
-            ? (launch_stft_cov<512, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, part, ctx->d_win, ctx->d_tw, c.length,
-                                           ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0))
-            : (launch_stft_cov<1024, false>(M, grid, (hipStream_t)s, y, mask_z, nullptr, part, ctx->d_win, ctx->d_tw, c.length,
-                                            ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)))
-        : STAGE(ctx, s, "stft_cov1", packed
-        ? (launch_stft_cov<512, true, true>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
-                                            ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0))
-        : c.n_fft == 512
-        ? launch_stft_cov<512>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
-                               ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0)
-        : launch_stft_cov<1024>(M, grid, (hipStream_t)s, y, mask_z, (c32*)X, part, ctx->d_win, ctx->d_tw, c.length,
-                                ctx->T, c.pad_mode, chunks, runw, ctx->d_lens, ctx->Kl, zero_beyond ? 1 : 0));
+    const auto launch = [&](auto n512, auto st, auto pack) {
+        constexpr int N = decltype(n512)::value ? 512 : 1024;
+        constexpr bool STORE = decltype(st)::value, PACK = decltype(pack)::value;
+        if constexpr (PACK && !(N == 512 && STORE)) {          // packed rows: 512 points, stored spectra (refused above otherwise)
+            return false;
+        } else {                                                // the 1024-point spectrum tile of 7-8 mics does not fit the 160 KiB LDS
+            return for_int<1, (N == 512 ? 8 : 6)>(M, [&](auto m) {
+                constexpr int M_ = decltype(m)::value;
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_cov<N, M_, STORE, PACK>), dim3((unsigned)(G * chunks)), dim3(64 * STFT_WAVES), 0,
+                                   (hipStream_t)s, y, mask_z, STORE ? (c32*)X : nullptr, part, ctx->d_win, ctx->d_tw, c.length, ctx->T, c.pad_mode, chunks,
+                                   runw, ctx->d_lens, ctx->Kl, o.zero_beyond ? 1 : 0);
+            });
+        }
+    };
+    const bool ok = STAGE(ctx, s, store ? "stft_cov1" : "stft_cov1_nostore", with_bool(c.n_fft == 512, [&](auto n512) {
+        return with_bool(store, [&](auto st) { return with_bool(packed, [&](auto pack) { return launch(n512, st, pack); }); });
+    }));
     if (!ok) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: unsupported mic count");
     partials_commit(ctx, chunks, M, false);
     // kept for a possible re-use by step 2, unless there is nothing to pair these sums with later (no spectra; a shard runs the staged step 2)
@@ -124,7 +92,9 @@ extern "C" int disco_selftest_stft_cov_packed(disco_ctx* ctx, const float* y, co
                                               disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
     if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_selftest_stft_cov_packed: Rss and Rnn must both be given or both be NULL");
-    int rc = stft_cov_partials(ctx, y, mask_z, X, s, true, true, true);
+    StftCovOpts o;
+    o.layout = XLayout::Packed;
+    int rc = stft_cov_partials(ctx, y, mask_z, X, s, o);
     if (rc || !Rss) return rc;
     return cov_finalize(ctx, Rss, Rnn, s);
 }

@@ -14,6 +14,7 @@
 
 #include "../../include/disco_hip.h"
 #include "common.h"
+#include "dispatch.h"
 
 
 using disco::c32;
@@ -207,17 +208,6 @@ static inline bool has_lengths(const disco_ctx* ctx) { return ctx->d_lens != nul
 // whole-path entry points work on all nodes of a room and on their own plain [R][K] exchanged-signal arrays
 static inline bool sharded(const disco_ctx* ctx) { return ctx->Kl != ctx->cfg.nodes || ctx->zblk != ctx->cfg.nodes; }
 
-// (M, KR) instantiation table: every split of P = M + KR <= 8 channels.
-#define DISCO_FOR_MKR(X_) \
-    X_(1, 0) X_(1, 1) X_(1, 2) X_(1, 3) X_(1, 4) X_(1, 5) X_(1, 6) X_(1, 7) \
-    X_(2, 0) X_(2, 1) X_(2, 2) X_(2, 3) X_(2, 4) X_(2, 5) X_(2, 6)          \
-    X_(3, 0) X_(3, 1) X_(3, 2) X_(3, 3) X_(3, 4) X_(3, 5)                   \
-    X_(4, 0) X_(4, 1) X_(4, 2) X_(4, 3) X_(4, 4)                            \
-    X_(5, 0) X_(5, 1) X_(5, 2) X_(5, 3)                                     \
-    X_(6, 0) X_(6, 1) X_(6, 2)                                              \
-    X_(7, 0) X_(7, 1)                                                       \
-    X_(8, 0)
-
 namespace disco_host {
 using disco::c32;
 struct WsLayout {
@@ -284,13 +274,25 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
 bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask);
 int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, disco_stream s,
                       bool store_z = true);
-int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, bool store = true,
-                      bool zero_beyond = true, bool packed = false);
+// rows of X: the public [T][F][M], or the packed workspace layout [T][F - 1][M] with the Nyquist bin in the DC slot (k_stft.h; 512 points)
+enum class XLayout { Public, Packed };
+// leading M x M block of the step-2 sums: accumulated with the rest, or step 1's -- the caller has checked that the step-1 partial sums of
+// THIS X with THIS mask are still kept (step1_held); the block is then neither accumulated nor written and the sums go to the tail block
+enum class LeadBlock { Accumulate, Step1 };
+// store = false (single-node path): the spectra are not written (X may be NULL); only for shapes the fused kernel takes
+// zero_beyond = false (per-room lengths): the frames of X beyond a room's clip are left unwritten -- only for a caller whose every reader of
+// X knows the lengths (the fused route of disco_tango_enhance)
+// layout = Packed: needs stored spectra -- the same partial sums
+struct StftCovOpts {
+    bool store = true, zero_beyond = true;
+    XLayout layout = XLayout::Public;
+};
+int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_stream s, const StftCovOpts& o = {});
 int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out, disco_stream s,
-                       bool skiploc = false, bool packed = false);
-// filter + iSTFT of the fused route (disco_step2_apply_istft_fused); packed: X in the packed workspace layout (k_stft.h)
+                       LeadBlock lead, XLayout layout);
+// filter + iSTFT of the fused route (disco_step2_apply_istft_fused)
 int step2_apply_istft(disco_ctx* ctx, const disco_c32* X, const disco_c32* w_loc, const disco_c32* w_glo, float* out, disco_stream s,
-                      bool packed);
+                      XLayout layout);
 int stft_apply_istft(disco_ctx* ctx, const float* y, const disco_c32* w, float* out, disco_stream s);
 bool step2_apply_istft_ok(const disco_ctx* ctx);
 bool apply_istft_wide_ok(const disco_ctx* ctx);

@@ -21,8 +21,8 @@ api_stft.hip; the CPU test reads the shape tables out of the headers and asserts
                                                                                 160 KiB (`apply_istft_shared_bytes`; all 36 fit)
     disco_apply_istft_fused                      k_apply_istft_wide<N, M, K-1>  N = 512 | 1024, the nine (M, K) of DISCO_FOR_WIDE_ISTFT
     disco_istft                                  k_istft<N, false>
-    UNREACHABLE (instantiated, never launched): k_apply_mq<4, 1> and <4, 3> (KR <= 4 with four microphones is in DISCO_FOR_MKR, and that
-        branch of api_apply.hip comes first), k_apply_m<4, 15> and <8, 15> (every M = 4 | 8 call with 1 <= KR <= 15 runs k_apply or
+    UNREACHABLE (instantiated, never launched): k_apply_mq<4, 1> and <4, 3> (KR <= 4 with four microphones is in DISCO_FOR_MKR, and disco_apply
+        tries for_mkr first), k_apply_m<4, 15> and <8, 15> (every M = 4 | 8 call with 1 <= KR <= 15 runs k_apply or
         k_apply_mq, and KR = 0 is in the table).
     ELSEWHERE: k_istft<N, true> (one frame per transform) belongs to the online entry points (tests/online_checks.py);
         k_stft_apply_istft takes its filter from the solve inside disco_tango_enhance and cannot be given taps: whole-path tests only
@@ -53,9 +53,9 @@ from cov_checks import HOP, MKR, _bits, _engine, _raises, _seed, kernel_key, z_t
 from oracle import stft_oracle as so
 
 BAR_FACTOR = 4.0
-ROOM = ((8, 8), (8, 6), (8, 4), (8, 2), (4, 8), (4, 6))                               # DISCO_FOR_ROOM (room_launch.h)
-WIDE_ISTFT = ROOM + ((4, 4), (4, 3), (4, 2))                                          # DISCO_FOR_WIDE_ISTFT (api_apply_istft_wide.hip)
-MQ = tuple((m, krt) for m in (4, 8) for krt in (1, 3, 7, 15))                         # the Q_ list (api_apply.hip)
+ROOM = ((8, 8), (8, 6), (8, 4), (8, 2), (4, 8), (4, 6))                               # DISCO_FOR_ROOM (dispatch.h)
+WIDE_ISTFT = ROOM + ((4, 4), (4, 3), (4, 2))                                          # DISCO_FOR_WIDE_ISTFT (dispatch.h)
+MQ = tuple((m, krt) for m in (4, 8) for krt in (1, 3, 7, 15))                         # DISCO_FOR_APPLY_MQ (dispatch.h)
 LDS_BUDGET = 160 * 1024
 UNREACHABLE = ('k_apply_mq<4,1>', 'k_apply_mq<4,3>', 'k_apply_m<4,15>', 'k_apply_m<8,15>')
 ELSEWHERE = {
@@ -125,7 +125,7 @@ def reachable():
 
 
 def instantiated():
-    """Every instantiation the dispatchers of the five files name."""
+    """Every instantiation the launches of the five files name (the shape tables of dispatch.h times their with_bool / for_int)."""
     inst = {f'k_apply<{m},{kr}>' for m, kr in MKR} | {f'k_apply_m<{m},{x}>' for m in range(1, 9) for x in (15, 31)}
     inst |= {f'k_apply_mq<{m},{krt}>' for m, krt in MQ} | {f'k_step2_apply_fused<{m},{kr + 1}>' for m, kr in MKR}
     inst |= {f'k_step2_apply_istft<512,{m},{kr + 1}>' for m, kr in MKR if apply_istft_shared_bytes(m, kr + 1) <= LDS_BUDGET}

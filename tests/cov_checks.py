@@ -20,8 +20,8 @@ tables out of the headers and asserts that `exact_cases` launches every name `ro
     disco_step2_cov_fused_reuse                 k_step2_cov_fused<M, K, true>  K >= 2
     disco_stft_cov_fused                        k_stft_cov<n_fft, M, true>     M <= 8 at 512 points, M <= 6 at 1024
                                                 k_stft + k_cov_loc_f64<M>      M = 7, 8 at 1024 points (the staged pair)
-    UNREACHABLE (instantiated, never launched): k_cov<7, 0, ..> and k_cov<8, 0, ..> (both hidden behind k_cov_loc_f64: the split test
-        of api_cov.hip comes first and (7, 0), (8, 0) are in DISCO_FOR_SPLIT_M8), k_cov<M, 0, false, ..> (a step-1 call has no Zn).
+    UNREACHABLE (instantiated, never launched): k_cov<7, 0, ..> and k_cov<8, 0, ..> (both hidden behind k_cov_loc_f64: cov_partials
+        walks DISCO_FOR_MKR only when its split test fails, and (7, 0), (8, 0) are in DISCO_FOR_SPLIT_M8), k_cov<M, 0, false, ..> (a step-1 call has no Zn).
     WHOLE PATH ONLY (not reachable from a staged call; run by tests/test_gpu_parity.py::test_room_cov_* / test_wide_* and
         tests/test_gpu_wide_network.py through disco_tango_enhance): k_cov_split_lds<M, KR, true>, k_room_cov.
 
@@ -67,9 +67,9 @@ BAR_FACTOR = 4.0
 
 # ---- the shape tables of the dispatch, restated (tests/test_cov_routes_cpu.py compares them with the headers) ---------------------------
 
-MKR = tuple((m, kr) for m in range(1, 9) for kr in range(0, 9 - m))                    # DISCO_FOR_MKR (host.h)
+MKR = tuple((m, kr) for m in range(1, 9) for kr in range(0, 9 - m))                    # DISCO_FOR_MKR (dispatch.h)
 SPLIT = ((7, 0), (8, 0)) + tuple((8, kr) for kr in range(1, 9)) + tuple((4, kr) for kr in range(5, 13)) \
-    + tuple((2, kr) for kr in range(7, 15))                                            # DISCO_FOR_SPLIT_M8 / M4 / M2 (cov_split_launch.h)
+    + tuple((2, kr) for kr in range(7, 15))                                            # DISCO_FOR_SPLIT_M8 / M4 / M2 (dispatch.h)
 CB_PMAX, CW_PMAX = 16, 32
 
 UNREACHABLE = tuple(f'k_cov<{m},0,{s},{nt}>' for m in (7, 8) for s in ('true', 'false') for nt in (320, 576)) \

@@ -26,19 +26,19 @@ def _table(text, macro):
 
 
 def test_shape_tables_are_the_sources():
-    assert _table(_read(CSRC, 'host.h'), 'DISCO_FOR_MKR') == ac.MKR and len(ac.MKR) == 36
-    assert _table(_read(CSRC, 'room_launch.h'), 'DISCO_FOR_ROOM') == ac.ROOM
-    wide = _read(CSRC, 'api_apply_istft_wide.hip')
-    body = re.search(r'#define DISCO_FOR_WIDE_ISTFT\(X_\) DISCO_FOR_ROOM\(X_\)([^\n]*)', wide).group(1)
+    tables = _read(CSRC, 'dispatch.h')
+    assert _table(tables, 'DISCO_FOR_MKR') == ac.MKR and len(ac.MKR) == 36
+    assert _table(tables, 'DISCO_FOR_ROOM') == ac.ROOM
+    body = re.search(r'#define DISCO_FOR_WIDE_ISTFT\(X_\) DISCO_FOR_ROOM\(X_\)([^\n]*)', tables).group(1)
     assert ac.ROOM + tuple((int(a), int(b)) for a, b in re.findall(r'X_\((\d+),\s*(\d+)\)', body)) == ac.WIDE_ISTFT and len(ac.WIDE_ISTFT) == 9
     api = _read(CSRC, 'api_apply.hip')
-    q_line = re.search(r'\n\s*(Q_\(4, 1\)[^\n]*)\n', api).group(1)
-    assert tuple((int(a), int(b)) for a, b in re.findall(r'Q_\((\d+),\s*(\d+)\)', q_line)) == ac.MQ
+    assert _table(tables, 'DISCO_FOR_APPLY_MQ') == ac.MQ and 'for_apply_mq(M, krt, [&](auto m, auto k) {' in api
     assert 'const int krt = KR <= 1 ? 1 : (KR <= 3 ? 3 : (KR <= 7 ? 7 : 15));' in api
     assert [ac.krt_of(kr) for kr in range(1, 16)] == [1, 3, 3] + [7] * 4 + [15] * 8
     # the LDS budget and the struct it is held against, member by member
     istft = _read(CSRC, 'api_step2_istft.hip')
-    assert istft.count('sizeof(ApplyIstftShared<512, M') == 2 and istft.count('<= 160 * 1024') == 2 and ac.LDS_BUDGET == 160 * 1024
+    assert 'constexpr bool apply_istft_fits = sizeof(ApplyIstftShared<512, M, K>) <= 160 * 1024;' in istft and ac.LDS_BUDGET == 160 * 1024
+    assert istft.count('apply_istft_fits<') == 2              # the predicate and the launch
     fused = _read(CSRC, 'k_fused.h')
     struct = re.search(r'struct alignas\(16\) ApplyIstftShared \{(.*?)\};', fused, re.S).group(1)
     assert [l.split(';')[0].strip() for l in struct.strip().splitlines()] == [
@@ -54,22 +54,26 @@ def test_route_restates_the_dispatch_order():
     """The statements of the dispatchers `route` leans on, in the order it assumes.  Pinned verbatim ON PURPOSE: a drift alarm.  Whoever
     reorders a dispatcher is sent here to restate the change in apply_checks.route, on which the coverage claim of the tier rests."""
     api = _read(CSRC, 'api_apply.hip')
-    marks = ['if (KR != 0 && KR != c.nodes - 1) return fail', 'if (M > 8) return fail', 'if (P > 32) return fail', 'DISCO_FOR_MKR(X_)',
-             'if ((M == 4 || M == 8) && KR >= 1 && KR <= 15) {', 'if (KR > 15) {', 'k_apply_m<M_, 31>', 'k_apply_m<M_>)']
+    marks = ['if (KR != 0 && KR != c.nodes - 1) return fail', 'if (M > 8) return fail', 'if (P > 32) return fail',
+             'const bool flat = for_mkr(M, KR, [&](auto m, auto kr) {', 'if (flat) return check_launch',
+             'if ((M == 4 || M == 8) && KR >= 1 && KR <= 15) {', 'if (KR > 15) {', 'k_apply_m<decltype(m)::value, 31>', 'k_apply_m<decltype(m)::value>)']
     at = [api.index(m) for m in marks]
     assert at == sorted(at)
-    assert 'C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8)' in api and 'template <int M, int KRMAX = 15>' in _read(CSRC, 'k_apply.h')
+    assert api.count('for_int<1, 8>(M, [&](auto m) {') == 2 and 'template <int M, int KRMAX = 15>' in _read(CSRC, 'k_apply.h')
     s2 = _read(CSRC, 'api_step2_apply.hip')
-    marks = ['if (sharded(ctx)) return fail', 'if (P > 8) return fail', 'M == M_ && K == KR_ + 1', 'k_step2_apply_fused<M_, KR_ + 1>']
+    marks = ['if (sharded(ctx)) return fail', 'if (P > 8) return fail', 'for_mkr(M, K - 1, [&](auto m, auto kr) {', 'K_ = decltype(kr)::value + 1;',
+             'k_step2_apply_fused<M_, K_>']
     assert [s2.index(m) for m in marks] == sorted(s2.index(m) for m in marks)
     si = _read(CSRC, 'api_step2_istft.hip')
-    marks = ['if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED', 'if (c.n_fft != 512 || P > 8) return fail', 'launch_apply_istft<M_, KR_ + 1>']
-    assert [si.index(m) for m in marks] == sorted(si.index(m) for m in marks) and 'k_step2_apply_istft<512, M, K>' in si
+    marks = ['if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED', 'if (c.n_fft != 512 || P > 8) return fail',
+             'for_mkr(M, K - 1, [&](auto m, auto kr) { with_bool(layout == XLayout::Packed', 'K_ = decltype(kr)::value + 1;',
+             'if constexpr (apply_istft_fits<M_, K_> && (!PACK || K_ >= 2)) {', 'k_step2_apply_istft<512, M_, K_, PACK>']
+    assert [si.index(m) for m in marks] == sorted(si.index(m) for m in marks)
     wide = _read(CSRC, 'api_apply_istft_wide.hip')
-    assert 'if (!wide_istft_shape(ctx->cfg)) return fail(ctx, DISCO_E_UNSUPPORTED' in wide and 'k_apply_istft_wide<1024, M_, K_ - 1>' in wide \
-        and 'k_apply_istft_wide<512, M_, K_ - 1>' in wide and 'const int K = c.nodes, WV = c.n_fft / 256;' in wide
+    assert 'if (!wide_istft_shape(ctx->cfg)) return fail(ctx, DISCO_E_UNSUPPORTED' in wide and 'constexpr int N = decltype(n1024)::value ? 1024 : 512, M_ = decltype(m)::value, KR_ = decltype(k)::value - 1;' in wide \
+        and 'k_apply_istft_wide<N, M_, KR_>' in wide and 'for_wide_istft(c.mics, K, [&](auto m, auto k) {' in wide and 'const int K = c.nodes, WV = c.n_fft / 256;' in wide
     stft = _read(CSRC, 'api_stft.hip')
-    assert 'return istft_any(ctx, Z, n_sig, out, ctx->cfg.length, ctx->T, s, false, ctx->d_lens, spr);' in stft and 'k_istft<512, false>' in stft
+    assert 'return istft_any(ctx, Z, n_sig, out, ctx->cfg.length, ctx->T, s, false, ctx->d_lens, spr);' in stft and 'k_istft<N, SOLO>' in stft
     assert 'constexpr int ISTFT_SEGS = ISTFT_FRAMES - 1;' in _read(CSRC, 'k_stft.h')
     # spot values
     r = ac.route

@@ -25,9 +25,9 @@ def _table(text, macro):
 
 
 def test_shape_tables_are_the_headers():
-    host, split = _read(CSRC, 'host.h'), _read(CSRC, 'cov_split_launch.h')
-    assert _table(host, 'DISCO_FOR_MKR') == cc.MKR and len(cc.MKR) == 36
-    got = _table(split, 'DISCO_FOR_SPLIT_M8') + _table(split, 'DISCO_FOR_SPLIT_M4') + _table(split, 'DISCO_FOR_SPLIT_M2')
+    tables = _read(CSRC, 'dispatch.h')
+    assert _table(tables, 'DISCO_FOR_MKR') == cc.MKR and len(cc.MKR) == 36
+    got = _table(tables, 'DISCO_FOR_SPLIT_M8') + _table(tables, 'DISCO_FOR_SPLIT_M4') + _table(tables, 'DISCO_FOR_SPLIT_M2')
     assert sorted(got) == sorted(cc.SPLIT) and len([s for s in got if s[1] > 0]) == 24
     assert int(re.search(r'constexpr int CB_PMAX = (\d+);', _read(CSRC, 'k_cov.h')).group(1)) == cc.CB_PMAX
     assert int(re.search(r'CW_PMAX = (\d+);', _read(CSRC, 'k_cov_wide.h')).group(1)) == cc.CW_PMAX
@@ -35,19 +35,23 @@ def test_shape_tables_are_the_headers():
 
 def test_route_restates_the_dispatch_order():
     """The statements of api_cov.hip `route` leans on, in the order it assumes: refusals, the wide route, the split test, the (M, KR)
-    table, k_cov_big.  The source lines are pinned verbatim ON PURPOSE: this is a drift alarm.  Whoever reorders or rewrites the dispatcher
-    is sent here to restate the change in cov_checks.route, on which the coverage claim of the whole tier rests."""
+    table (taken only when the split test fails), the split kernels, k_cov_big.  The source lines are pinned verbatim ON PURPOSE: this is a
+    drift alarm.  Whoever reorders or rewrites the dispatcher is sent here to restate the change in cov_checks.route, on which the coverage
+    claim of the whole tier rests."""
     api = _read(CSRC, 'api_cov.hip')
     marks = ['if (M > 8) return fail', 'if (P > CW_PMAX) return fail', 'if (P > CB_PMAX) return cov_partials_wide',
              'const bool split = (KR == 0 || (P > 8 && same && mask_remote && (ctx->F - 1) % 64 == 0)) && cov_split_shape(M, KR);',
-             'launched = launch_cov_split_shape(', 'DISCO_FOR_MKR(X_)', 'k_cov_big<true>']
+             'const bool mkr = !split && for_mkr(M, KR, [&](auto m, auto kr) {', 'if (!mkr) {', 'if (split)',
+             'launch_cov_split_shape(M, KR, skiploc, (unsigned)nblk, st, a);', 'k_cov_big<SAMEZ>']
     at = [api.index(m) for m in marks]
     assert at == sorted(at)
-    assert 'if (KR_ == 0 || same)' in api and 'if (Zs == Zn)' in api
+    assert api.count('with_bool(KR == 0 || same, [&](auto samez) {') == 2 and 'with_bool(Zs == Zn, [&](auto samez) {' in api
+    assert 'k_cov<M_, KR_, SAMEZ, NT>' in api and 'k_cov_wide<SAMEZ>' in api and api.count('constexpr bool SAMEZ = decltype(samez)::value;') == 3 and 'NT = decltype(n512)::value ? 320 : 576;' in api
     launch = _read(CSRC, 'cov_split_launch.h')
-    assert 'k_cov_loc_f64<M>' in launch and 'k_cov_split_lds<M, KR, false>' in launch
+    assert 'k_cov_loc_f64<M>' in launch and 'k_cov_split_lds<M, KR, SKIP>' in launch and 'constexpr bool SKIP = KR > 0 && decltype(skip)::value;' in launch
     step2 = _read(CSRC, 'api_step2_cov.hip')
-    assert 'if (P > 8) return fail' in step2 and 'k_step2_cov_fused<M_, KR_ + 1, false>' in step2 and 'M == M_ && K == KR_ + 1' in step2
+    assert 'if (P > 8) return fail' in step2 and 'k_step2_cov_fused<M_, K_, SKIPLOC, PACK>' in step2 \
+        and 'for_mkr(M, K - 1, [&](auto m, auto kr) {' in step2 and 'K_ = decltype(kr)::value + 1;' in step2
     stft = _read(CSRC, 'api_stft_cov.hip')
     assert 'if (c.n_fft == 1024 && M > 6)' in stft
     # spot values
