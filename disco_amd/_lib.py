@@ -92,6 +92,8 @@ PROTOTYPES = {
     'disco_lag_corr': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _sz, _vp]),
     'disco_bss_workspace_bytes': (_sz, [_vp, _i64, _int, _int, _i64]),
     'disco_bss_eval': (_int, [_vp, _vp, _vp, _i64, _int, _int, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    'disco_stoi_workspace_bytes': (_sz, [_vp, _i64, _i64, _int, _int, _int]),
+    'disco_stoi': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
     'disco_reference_workspace_bytes': (_sz, [_vp]),
     'disco_tango_reference': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, C.POINTER(DiscoRefOutputs), _vp, _sz, _vp]),
     'disco_tango_enhance_iterated': (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

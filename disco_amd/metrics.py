@@ -11,6 +11,9 @@ clipping / importance-weight arithmetic of the reference is applied to those.
     si_bss                    metrics.py:282-340      (SI-SDR / SI-SIR / SI-SAR against n_src references)
     bss_eval_sources          mir_eval.separation.bss_eval_sources as tango.py:541-567 calls it (SDR / SIR / SAR through a 512-tap
                               filtered projection; third-party and absent here: restated from its definition, csrc/k_bss.h)
+    stoi                      pystoi.stoi as tango.py:569-578 calls it (third-party and absent here: restated from its definition with
+                              pystoi's constants, csrc/k_stoi.h; pinned by the float64 yardstick of tests/stoi_checks.py, unpinned
+                              against the package)
     third_octave_filterbank   sigproc_utils.py:90-116
 
 `start` / `stop` select the scored span; the reference scores [fs : min_len] (tango.py:541-593), i.e. start = 16000.
@@ -191,6 +194,39 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
     else:
         perm = np.broadcast_to(idx, (n_set, nsrc)).copy()
     return tuple(v.reshape(lead + (nsrc,)) for v in (sdr, sir, sar, perm))
+
+
+def stoi(x, y, fs_sig, extended=False, start=0, stop=None):
+    """pystoi.stoi (name, argument order): x clean, y processed, (L,) -> float, or (..., L) batched over the leading axes -> (...);
+    NumPy arrays (copied) or device-resident (n_pair, L) tensors (read in place).  Both are resampled to 10 kHz, the frames of x more
+    than 40 dB below its loudest are removed from both, and the third-octave envelopes of every 30-frame segment are normalised,
+    clipped and correlated, all on the GPU (Engine.stoi, csrc/k_stoi.h).  `start` / `stop` select the scored span; `stop` may be an
+    array shaped like the leading axes, so that a batch of different clip lengths scores every pair as if it ran alone.
+    Fewer than 30 frames after the removal: 1e-5 and a RuntimeWarning, as pystoi.  A span too short for a single frame (fewer than 257
+    samples at 10 kHz) raises ValueError naming the pair.  extended=True (ESTOI) is not offered."""
+    if extended:
+        raise NotImplementedError('extended STOI (ESTOI) is not offered')
+    if isinstance(x, np.ndarray) or not hasattr(x, 'data_ptr'):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+    if isinstance(y, np.ndarray) or not hasattr(y, 'data_ptr'):
+        y = np.ascontiguousarray(y, dtype=np.float32)
+    shape = tuple(int(v) for v in x.shape)
+    if len(shape) < 1 or tuple(int(v) for v in y.shape) != shape:
+        raise ValueError(f'x and y should have the same length, found {shape} and {tuple(y.shape)}')
+    lead, L = shape[:-1], shape[-1]
+    n_pair = int(np.prod(lead, dtype=np.int64))
+    if stop is not None and np.ndim(stop):
+        stop = np.broadcast_to(np.asarray(stop), lead).reshape(n_pair)
+    d, status = _engine().stoi(x.reshape(n_pair, L), y.reshape(n_pair, L), fs_sig, start, stop)
+    if np.any(status == 2):
+        i = int(np.flatnonzero(status == 2)[0])
+        where = tuple(int(v) for v in np.unravel_index(i, lead)) if lead else ()
+        raise ValueError(f'pair {where}: the scored span is too short for one frame (fewer than 257 samples at 10 kHz)')
+    if np.any(status == 1):
+        import warnings
+        warnings.warn('Not enough STFT frames to compute intermediate intelligibility measure after removing silent frames. '
+                      'Returning 1e-5. Please check you wav files', RuntimeWarning)
+    return d.reshape(lead) if lead else float(d[0])
 
 
 def band_importance(fs):

@@ -11,8 +11,8 @@ input that is 16-bit PCM, full scale at +-1.0.  Here the standard library's `wav
 (samples = round(clip(x, -1, 1 - 2^-15) * 32768)); bit-level equality with libsndfile's rounding is not pinned.
 
 And the two result pickles of tango.py:617-635 (`room_results`, `write_result_pickles`): the level metrics and, given the mixture and
-the two enhanced mixtures in time, the eleven BSS-eval keys (SDR / SIR / SAR, what the reference takes from mir_eval), all scored on
-the GPU by disco_amd.metrics; the STOI keys (pystoi) hold NaN.
+the two enhanced mixtures in time, the eleven BSS-eval keys (SDR / SIR / SAR, what the reference takes from mir_eval) and, with `stoi=True`, the three
+STOI keys (what it takes from pystoi), all scored on the GPU by disco_amd.metrics.
 """
 import os
 import wave
@@ -76,8 +76,10 @@ def write_room_results(root, i_rir, noise, signals, masks_z=None, mask_w=None, f
 # fw_sd: the reference's own disco_theque/metrics.py) are computed by disco_amd.metrics on the GPU.  The eleven keys the reference
 # fills from mir_eval.separation.bss_eval_sources (BSS_KEYS) are computed on the GPU too, by disco_amd.metrics.bss_eval_sources
 # (restated from the definition of BSS-eval; mir_eval itself is third-party and absent), when room_results is given the time
-# signals they need (y_in, sh_t, szh_t); without them they hold NaN.  The keys filled from pystoi.stoi (third-party, absent: the
-# delta_stoi* keys) are present and always hold NaN, so that code reading the pickles finds every key it expects.
+# signals they need (y_in, sh_t, szh_t); without them they hold NaN.  The keys the reference fills from pystoi.stoi (STOI_KEYS) are
+# computed by disco_amd.metrics.stoi (restated from the definition of STOI with pystoi's constants; the package is third-party, absent
+# and the restatement unpinned against it) when room_results is given the same signals and `stoi=True`; otherwise they are present and
+# hold NaN, so that code reading the pickles finds every key it expects.
 RESULT_KEYS_TANGO = ('snr_in_raw', 'sar_cnv', 'sir_cnv', 'sdr_cnv', 'delta_stoi_cnv', 'delta_stoi_dry', 'snr_out', 'snr_in_cnv',
                      'snr_in_dry', 'fw_sd_cnv', 'fw_sd_dry', 'sar_dry', 'sir_dry', 'sdr_dry', 'sdr_in_cnv', 'sir_in_cnv',
                      'sdr_in_dry', 'sir_in_dry', 'sar_in_dry')
@@ -85,10 +87,11 @@ RESULT_KEYS_MWF = tuple('delta_stoi' if k == 'delta_stoi_cnv' else k for k in RE
 THIRD_PARTY_KEYS = ('sar_cnv', 'sir_cnv', 'sdr_cnv', 'delta_stoi_cnv', 'delta_stoi', 'delta_stoi_dry', 'sar_dry', 'sir_dry', 'sdr_dry',
                     'sdr_in_cnv', 'sir_in_cnv', 'sdr_in_dry', 'sir_in_dry', 'sar_in_dry')
 BSS_KEYS = tuple(k for k in THIRD_PARTY_KEYS if 'stoi' not in k)
+STOI_KEYS = tuple(k for k in THIRD_PARTY_KEYS if 'stoi' in k)
 
 
 def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
-                 bss_flen=512):
+                 bss_flen=512, stoi=False):
     """The two result dictionaries of one (room, noise) (tango.py:541-635).
     s_in, n_in (K, L): target / noise images at every node's first microphone; sf_t, nf_t (K, L): their step-2 outputs in time;
     szf_t, nzf_t (K, L): their compressed (step-1) versions in time; rnd_snrs: the drawn input SNRs; s_dry, n_dry (L,): the dry
@@ -97,7 +100,11 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
     three are given, the eleven BSS-eval keys (BSS_KEYS) are filled as tango.py:541-567 fills them: references (s_in[k], n_in[k]) for the
     `_cnv` keys and (s_dry, n_dry) for the `_dry` ones; estimates (sh, y - sh) for `res`, (szh, y - szh) for `resz`, (y, y - sh) for the
     `_in_` keys of both; source 0's figures; compute_permutation=False; a `bss_flen`-tap filter (mir_eval's 512).  The differences are
-    formed in float64 and rounded to float32 once, which is what the kernels read.  Without them those keys hold NaN."""
+    formed in float64 and rounded to float32 once, which is what the kernels read.  Without them those keys hold NaN.
+    stoi=True, with the same three signals: the STOI keys (STOI_KEYS) are filled as tango.py:569-578 fills them -- `delta_stoi_cnv` of `res`
+    and `delta_stoi` of `resz` are STOI(s_in[k], sh[k]) and STOI(s_in[k], szh[k]) minus STOI(s_in[k], y[k]); with the dry sources,
+    `delta_stoi_dry` of both likewise with s_dry as the clean signal.  All 6 K pairs of the room go in one Engine.stoi call.  The default
+    leaves those keys NaN."""
     from .. import metrics as dm
     K = np.shape(s_in)[0]
     bss = y_in is not None and sh_t is not None and szh_t is not None
@@ -147,6 +154,16 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
             res['sdr_in_dry'] = resz['sdr_in_dry'] = sdr[:, 2]
             res['sir_in_dry'] = resz['sir_in_dry'] = sir[:, 2]
             res['sar_in_dry'] = resz['sar_in_dry'] = sar[:, 2]
+    if stoi and bss:
+        clean = [cut(s_in)] + ([np.repeat(cut(s_dry)[None], K, axis=0)] if s_dry is not None else [])
+        proc = np.stack([cut(y_in), cut(sh_t), cut(szh_t)])                                # (3, K, L'): in, out, out_z
+        x = np.stack([np.broadcast_to(c, proc.shape) for c in clean])                      # (1 or 2, 3, K, L')
+        d = np.asarray(dm.stoi(x, np.broadcast_to(proc, x.shape), fs))                     # tango.py:569-574
+        res['delta_stoi_cnv'] = d[0, 1] - d[0, 0]                                          # :575
+        resz['delta_stoi'] = d[0, 2] - d[0, 0]                                             # :577
+        if s_dry is not None:
+            res['delta_stoi_dry'] = d[1, 1] - d[1, 0]                                      # :576
+            resz['delta_stoi_dry'] = d[1, 2] - d[1, 0]                                     # :578
     return res, resz
 
 

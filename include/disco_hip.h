@@ -551,6 +551,26 @@ int disco_bss_eval(disco_ctx* ctx, const float* refs, const float* ests, int64_t
                    int stop, int flen, int all_pairs, double* out, int32_t* status, void* workspace, size_t workspace_bytes,
                    disco_stream s);
 
+/* ---- STOI (what tango.py:569-578 takes from pystoi.stoi) ------------------------------------------------------------
+ * Restated from its definition (Taal, Hendriks, Heusdens, Jensen 2011) with pystoi's constants and conventions; not extended
+ * (ESTOI).  x [n_pair][len] clean, y [n_pair][len] processed, float; pair i is scored over [start, stop[i]) (stop: device array
+ * of n_pair int32, clamped into [start, len]; NULL = len for every pair).  p / q = 10000 / fs_sig in lowest terms; p == q: the
+ * signals are at 10 kHz already and taps is not read.  Otherwise taps [n_taps] float64 (device memory, n_taps = 2 L + 1 odd, at
+ * most 65536 -- DISCO_E_UNSUPPORTED beyond) is the normalised anti-aliasing filter h of pystoi's resample_oct and both signals
+ * are resampled as scipy.signal.resample_poly(x, p, q, window = h): out[m] = p sum_i h[m q + L - p i] x[i], ceil(n p / q) samples.
+ * Then: frames of 256 samples at hop 128 windowed by hanning(258)[1:-1]; the frames of x within 40 dB of its loudest are kept
+ * (the same frames of y), overlap-added, framed and windowed again, transformed (512 points), summed over 15 third-octave bands
+ * from 150 Hz; every run of 30 frames of every band is normalised, clipped at -15 dB SDR, centred and correlated.
+ *   out[i][2] = { d, number of kept frames };  status[i] (int32): 0 scored; 1 fewer than 30 frames after the removal, d = 1e-5
+ *   (pystoi warns and returns that); 2 the span gives no frame at all (fewer than 257 samples at 10 kHz), d = NaN.
+ * An all-zero x gives d = 0.  A pair's result is bit-identical from run to run and whatever else is in the batch (no atomics).
+ * workspace: at least disco_stoi_workspace_bytes(ctx, n_pair, len, p, q, n_taps) -- the two resampled signals (8 ceil(len p / q)
+ * bytes per pair, none at 10 kHz), frame energies and indices, the band spectra (120 bytes per frame) and partial sums;
+ * 0 for a shape disco_stoi refuses. */
+size_t disco_stoi_workspace_bytes(const disco_ctx* ctx, int64_t n_pair, int64_t len, int p, int q, int n_taps);
+int disco_stoi(disco_ctx* ctx, const float* x, const float* y, int64_t n_pair, int64_t len, int start, const int32_t* stop, int p, int q,
+               const double* taps, int n_taps, double* out, int32_t* status, void* workspace, size_t workspace_bytes, disco_stream s);
+
 /* ---- the step before the path: reverberation of dry signals ------------------------------------
  * out[i][c][0:out_len] = np.convolve(dry[i], rir[i][c])[:out_len]  (zero beyond dry_len + rir_len - 1), the operation of
  * dataset_generation/gen_disco/convolve_signals.py:160-163 (and of pyroomacoustics' room.simulate, :94-97), batched:
