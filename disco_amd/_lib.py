@@ -85,6 +85,9 @@ PROTOTYPES = {
     'disco_conv3x3_pool4': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
     'disco_crnn_features': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, C.c_float, C.c_float, _vp, _vp]),
     'disco_crnn_windows': (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp]),
+    'disco_crnn_features_rooms': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, C.c_float, C.c_float, _vp, _vp, _vp]),
+    'disco_crnn_windows_rooms': (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _i64, _vp]),
+    'disco_crnn_expand_rows': (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     'disco_pair_stats': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     'disco_band_stats': (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _int, _vp, _vp]),
     'disco_band_stats_gated': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _int, _vp, _vp]),

@@ -11,6 +11,9 @@
 using namespace disco;
 using namespace disco_host;
 
+// grid cap of the mixed-length CRNN helpers (bandwidth kernels in a grid-stride loop: 64 workgroups per CU are plenty)
+static constexpr long long RAGGED_MAX_BLOCKS = 1 << 14;
+
 // ---- helper of the mask-estimation DNN (disco_amd/dnn/crnn.py): the pointwise half of a GRU step -----------------------------
 extern "C" int disco_gru_gates(disco_ctx* ctx, const float* gi, int64_t gi_stride, const float* gh, const float* gh_bias,
                                const float* h_prev, float* h_out, int64_t n, int H, disco_stream s) {
@@ -80,6 +83,20 @@ extern "C" int disco_crnn_features(disco_ctx* ctx, const disco_c32* X, const dis
     return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
 }
 
+// rooms of different clip lengths (disco_set_lengths): frames[r] = T_r of room r, rows at and beyond it are exact zeros
+extern "C" int disco_crnn_features_rooms(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, int64_t R, int K, int M, int T, int F, int mic, int pad_lo,
+                                         int pad_hi, float lo, float hi, const int32_t* frames, float* out, disco_stream s) {
+    if (!X || !out || !frames || R < 1 || K < 1 || M < 1 || T < 1 || F < 1 || mic < 0 || mic >= M || pad_lo < 0 || pad_hi < 0 || !(lo <= hi))
+        return ctx ? fail(ctx, DISCO_E_ARG, "disco_crnn_features_rooms: bad argument") : DISCO_E_ARG;
+    DevGuard dev_guard_(ctx ? ctx->cfg.device : [] { int d = 0; (void)hipGetDevice(&d); return d; }());
+    const int C = Z ? K : 1, Tp = pad_lo + T + pad_hi;
+    const long long total = (long long)R * K * C * Tp * F;
+    hipLaunchKernelGGL(k_crnn_features_rooms, dim3((unsigned)std::min<long long>((total + 255) / 256, RAGGED_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)s,
+                       (const c32*)X, (const c32*)Z, (const int*)frames, out, (long long)R, K, M, T, F, C, mic, pad_lo, Tp, lo, hi);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
+}
+
 extern "C" int disco_selftest_pk(disco_ctx* ctx, const disco_c32* a, const disco_c32* b, const disco_c32* c, int64_t n,
                                  disco_c32* out_hw, disco_c32* out_ref, disco_stream s) {
     static_assert(PK_SELFTEST_OPS == DISCO_PK_SELFTEST_OPS, "header and kernel disagree");
@@ -110,6 +127,36 @@ extern "C" int disco_crnn_windows(disco_ctx* ctx, const float* feat, int64_t B, 
     const long long total = (long long)B * T * (n_keep / 4);
     hipLaunchKernelGGL(k_crnn_windows, dim3((unsigned)std::min<long long>((total + 255) / 256, 1 << 20)), dim3(256), 0, (hipStream_t)s,
                        (const float4*)feat, (float4*)out, (long long)B, C, Tp, T, W, n_keep / 4);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
+}
+
+extern "C" int disco_crnn_windows_rooms(disco_ctx* ctx, const float* feat, int64_t B, int C, int Tp, int T, int W, int n_keep, const int32_t* frames_sig,
+                                        const int64_t* row0, float* out, int64_t n_rows, disco_stream s) {
+    if (!feat || !out || !frames_sig || !row0 || B < 1 || C < 1 || T < 1 || W < 1 || Tp < T + W - 1 || n_keep < 4 || n_keep % 4 || n_keep > C * W * 4 ||
+        n_rows < 1 || ((uintptr_t)feat & 15) || ((uintptr_t)out & 15))
+        return ctx ? fail(ctx, DISCO_E_ARG, "disco_crnn_windows_rooms: bad argument") : DISCO_E_ARG;
+    DevGuard dev_guard_(ctx ? ctx->cfg.device : [] { int d = 0; (void)hipGetDevice(&d); return d; }());
+    const long long total = (long long)B * T * (n_keep / 4);
+    hipLaunchKernelGGL(k_crnn_windows_rooms, dim3((unsigned)std::min<long long>((total + 255) / 256, RAGGED_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)s,
+                       (const float4*)feat, (float4*)out, (const int*)frames_sig, (const long long*)row0, (long long)B, C, Tp, T, W, n_keep / 4,
+                       (long long)n_rows);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
+}
+
+extern "C" int disco_crnn_expand_rows(disco_ctx* ctx, const float* rows, int64_t n_rows, int64_t B, int T, int F, const int32_t* frames_sig,
+                                      const int64_t* row0, float* out, disco_stream s) {
+    if (!rows || !out || !frames_sig || !row0 || n_rows < 1 || B < 1 || T < 1 || F < 1 || ((uintptr_t)rows & 3) || ((uintptr_t)out & 3))
+        return ctx ? fail(ctx, DISCO_E_ARG, "disco_crnn_expand_rows: bad argument") : DISCO_E_ARG;
+    DevGuard dev_guard_(ctx ? ctx->cfg.device : [] { int d = 0; (void)hipGetDevice(&d); return d; }());
+    const long long total = (long long)B * T * F;
+    if (((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_crnn_expand_rows<4>), dim3((unsigned)std::min<long long>(((total + 3) / 4 + 255) / 256, RAGGED_MAX_BLOCKS)),
+                           dim3(256), 0, (hipStream_t)s, rows, out, (const int*)frames_sig, (const long long*)row0, (long long)B, T, F, (long long)n_rows);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_crnn_expand_rows<1>), dim3((unsigned)std::min<long long>((total + 255) / 256, RAGGED_MAX_BLOCKS)), dim3(256), 0,
+                           (hipStream_t)s, rows, out, (const int*)frames_sig, (const long long*)row0, (long long)B, T, F, (long long)n_rows);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
 }

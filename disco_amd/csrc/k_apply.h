@@ -348,4 +348,67 @@ static __global__ void k_crnn_windows(const float4* __restrict__ feat, float4* _
     }
 }
 
+// The windows of the EXISTING frames only, compacted: signal b has frames_sig[b] <= T frames and its window t goes to row row0[b] + t (row0 = exclusive
+// prefix sum of frames_sig), the same 16 bytes per thread as k_crnn_windows writes to row b T + t.  The grid walks the rectangle (b, t, e4); threads of
+// t >= frames_sig[b], or of a row outside [0, n_rows), touch no memory.
+static __global__ void k_crnn_windows_rooms(const float4* __restrict__ feat, float4* __restrict__ out, const int* __restrict__ frames_sig,
+                                            const long long* __restrict__ row0, long long B, int C, int Tp, int T, int W, int n_keep4, long long n_rows) {
+    const long long total = B * T * n_keep4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int e4 = (int)(i % n_keep4);
+        const long long bt = i / n_keep4;
+        const int t = (int)(bt % T);
+        const long long b = bt / T;
+        if (t >= frames_sig[b]) continue;
+        const long long row = row0[b] + t;
+        if (row < 0 || row >= n_rows) continue;
+        const int c = e4 / W, w = e4 - c * W;
+        out[row * n_keep4 + e4] = feat[(b * C + c) * Tp + t + w];
+    }
+}
+
+// The inverse placement for the output layer: out [B][T][F] <- rows [n_rows][F], out[b][t] = rows[row0[b] + t] for t < frames_sig[b] and exact zeros
+// beyond; every element of out is written, V = 4 floats (one 16-byte store) or 1 per thread.  F is odd for the CRNN (257), so the rows of `rows` and of
+// `out` keep no alignment of their own: out is walked as ONE flat array from its aligned base, the loads are single dwords (consecutive lanes read
+// consecutive addresses within a row).
+template <int V>
+static __global__ void k_crnn_expand_rows(const float* __restrict__ rows, float* __restrict__ out, const int* __restrict__ frames_sig,
+                                          const long long* __restrict__ row0, long long B, int T, int F, long long n_rows) {
+    const long long total = B * T * F, n_vec = (total + V - 1) / V;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += (long long)gridDim.x * blockDim.x) {
+        const long long e0 = i * V;
+        long long bt = e0 / F;
+        int f = (int)(e0 - bt * F);
+        float v[V];
+        const float* src = nullptr;
+        bool fresh = true;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (fresh) {                                    // a new (b, t): where its row lies, if it exists
+                const long long b = bt / T;
+                const int t = (int)(bt - b * T);
+                src = nullptr;
+                if (b < B && t < frames_sig[b]) {
+                    const long long row = row0[b] + t;
+                    if (row >= 0 && row < n_rows) src = rows + row * F;
+                }
+                fresh = false;
+            }
+            v[j] = src ? src[f] : 0.f;
+            if (++f == F) {
+                f = 0;
+                ++bt;
+                fresh = true;
+            }
+        }
+        if (V == 4 && e0 + 4 <= total) {
+            *(float4*)(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (e0 + j < total) out[e0 + j] = v[j];
+        }
+    }
+}
+
 }  // namespace disco

@@ -76,6 +76,21 @@ static __global__ __launch_bounds__(256) void k_conv3x3_pool4_direct(const float
     }
 }
 
+// one element of the map: clip(|.|, lo, hi) of X's microphone (c == 0) or of the (c - 1)-th other node's Z, frame t of signal g = (room, node)
+static __device__ __forceinline__ float crnn_feature_at(const c32* __restrict__ X, const c32* __restrict__ Z, long long g, int c, int t, int f, int K, int M,
+                                                        int T, int F, int mic, float lo, float hi) {
+    c32 a;
+    if (c == 0) {
+        a = X[((g * T + t) * F + f) * (long long)M + mic];
+    } else {
+        const int k = (int)(g % K), j = (c - 1) < k ? (c - 1) : c;            // the (c - 1)-th node other than k
+        a = Z[(((g / K) * K + j) * T + t) * (long long)F + f];
+    }
+    // |a|^2 with its fma written out: hipcc's contraction chose fma(a.x, a.x, a.y a.y) here, but its choice follows the code around it
+    const float m = sqrtf(fmaf(a.x, a.x, a.y * a.y));
+    return m != m ? m : fminf(fmaxf(m, lo), hi);     // NaN passes, as np.clip / torch.clamp leave it (fmaxf would make it lo)
+}
+
 // The networks' input features in one pass (speech_enhancement/utils.py:69-138 prepare_data; tango.py:338, 391, 158-186): out [R K][C][pad_lo + T +
 // pad_hi][F] float = clip(|.|, lo, hi) of, channel 0, microphone `mic` of the node's own spectra X [R][K][T][F][M] and, channels 1 ... K - 1 (C = K: the
 // step-2 network), the compressed signals Z [R][K][T][F] of the OTHER nodes in node order (get_z_for_mask 'zs_hat'); zeros in the padding rows (the
@@ -92,18 +107,26 @@ static __global__ void k_crnn_features(const c32* __restrict__ X, const c32* __r
         const long long g = q / C;                          // (room, node)
         const int t = tp - pad_lo;
         float v = 0.f;
-        if (t >= 0 && t < T) {
-            c32 a;
-            if (c == 0) {
-                a = X[((g * T + t) * F + f) * (long long)M + mic];
-            } else {
-                const int k = (int)(g % K), j = (c - 1) < k ? (c - 1) : c;            // the (c - 1)-th node other than k
-                a = Z[(((g / K) * K + j) * T + t) * (long long)F + f];
-            }
-            // |a|^2 with its fma written out: hipcc's contraction chose fma(a.x, a.x, a.y a.y) here, but its choice follows the code around it
-            const float m = sqrtf(fmaf(a.x, a.x, a.y * a.y));
-            v = m != m ? m : fminf(fmaxf(m, lo), hi);     // NaN passes, as np.clip / torch.clamp leave it (fmaxf would make it lo)
-        }
+        if (t >= 0 && t < T) v = crnn_feature_at(X, Z, g, c, t, f, K, M, T, F, mic, lo, hi);
+        out[i] = v;
+    }
+}
+
+// The same map for a batch whose rooms differ in clip length: room r has frames[r] <= T frames; every row at or beyond that is an exact zero like the
+// padding rows (the reference pads zeros AFTER the clip, so a missing frame is 0 and not `lo`), and what X / Z hold there is never read.
+static __global__ void k_crnn_features_rooms(const c32* __restrict__ X, const c32* __restrict__ Z, const int* __restrict__ frames, float* __restrict__ out,
+                                             long long R, int K, int M, int T, int F, int C, int mic, int pad_lo, int Tp, float lo, float hi) {
+    const long long total = R * K * C * Tp * F;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int f = (int)(i % F);
+        long long q = i / F;
+        const int tp = (int)(q % Tp);
+        q /= Tp;
+        const int c = (int)(q % C);
+        const long long g = q / C;                          // (room, node)
+        const int t = tp - pad_lo;
+        float v = 0.f;
+        if (t >= 0 && t < T && t < frames[g / K]) v = crnn_feature_at(X, Z, g, c, t, f, K, M, T, F, mic, lo, hi);
         out[i] = v;
     }
 }

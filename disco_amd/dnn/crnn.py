@@ -13,6 +13,8 @@ Two evaluation paths with identical results:
     that; the reference's `.view` (which re-interprets the (64, 15, 4) block as (15, 256) WITHOUT a transpose,
     crnn.py:59) is reproduced on the slices; only the 8 GRU steps that reach output frame 7 are run.
 """
+import functools
+
 import numpy as np
 import torch
 from torch import nn
@@ -72,23 +74,72 @@ def _conv3x3_pool4_hip(x, w, b):
     return out
 
 
-def crnn_features_hip(X, z, mic, pad, lo=STFT_MIN, hi=STFT_MAX):
+def crnn_features_hip(X, z, mic, pad, lo=STFT_MIN, hi=STFT_MAX, frames=None):
     """The networks' input features in one pass on the GPU (disco_crnn_features): X (R, K, T, F, M) complex64 spectra, z (R, K, T, F)
     complex64 compressed signals or None -> float32 (R K, C, pad[0] + T + pad[1], F), C = 1 (z None: |X[..., mic]|) or K (|X[..., mic]| then
     the |z| of the other nodes in node order, get_z_for_mask 'zs_hat'); clipped to [lo, hi], zero rows as padding (prepare_data pads after
-    clipping).  What `predict_masks(..., prepared=True)` takes."""
+    clipping).  What `predict_masks(..., prepared=True)` takes.
+    frames: (R,) frames T_r <= T each ROOM has (Engine.frames; a host sequence, or an int32 tensor already on X's device), for a batch whose
+    rooms differ in clip length (disco_crnn_features_rooms): the rows of the frames a room does not have are exact zeros like the padding
+    -- not zeros clipped up to `lo` -- which is what the room's own padding holds when it is run alone."""
     from .. import _lib
     lib = _lib.load()
     R, K, T, F, M = X.shape
     assert X.is_contiguous() and X.dtype == torch.complex64 and (z is None or (z.is_contiguous() and tuple(z.shape) == (R, K, T, F)))
     C_ = 1 if z is None else K
     out = torch.empty((R * K, C_, pad[0] + T + pad[1], F), dtype=torch.float32, device=X.device)
+    head = (None, X.data_ptr(), None if z is None else z.data_ptr(), R, K, M, T, F, int(mic), int(pad[0]), int(pad[1]), float(lo), float(hi))
     with torch.cuda.device(X.device):
-        rc = lib.disco_crnn_features(None, X.data_ptr(), None if z is None else z.data_ptr(), R, K, M, T, F, int(mic), int(pad[0]), int(pad[1]),
-                                     float(lo), float(hi), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if frames is None:
+            rc = lib.disco_crnn_features(*head, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        else:
+            fr = _frames_on(frames, R, T, X.device, host=False)[1]
+            rc = lib.disco_crnn_features_rooms(*head, fr.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
     if rc != 0:
-        raise RuntimeError(f'disco_crnn_features failed ({rc})')
+        raise RuntimeError(f'disco_crnn_features{"" if frames is None else "_rooms"} failed ({rc})')
     return out
+
+
+def _frames_on(frames, n, T, device, host=True):
+    """`frames` (n values 0 <= T_b <= T: a host sequence, or an integer tensor) -> (int64 host array, int32 tensor on `device`).  host=False:
+    a tensor that already lives on a GPU is taken as it is, unchecked, and no host copy is made of it (None comes back in its place).
+    The device copy of a host sequence is made once per distinct content (_frames_dev): a batch that keeps its lengths from step to step
+    issues no host-to-device copy after the first."""
+    if torch.is_tensor(frames) and frames.is_cuda and not host:
+        assert frames.numel() == n, (frames.numel(), n)
+        return None, frames.to(device=device, dtype=torch.int32).contiguous().view(-1)
+    h = np.asarray(frames.cpu() if torch.is_tensor(frames) else frames).reshape(-1).astype(np.int64)
+    if h.shape[0] != n or h.min() < 0 or h.max() > T:
+        raise ValueError(f'frames: {n} values in [0, {T}] expected, got {h.shape[0]} in [{h.min()}, {h.max()}]')
+    return h, _frames_dev(h.tobytes(), torch.device(device))
+
+
+@functools.lru_cache(maxsize=16)
+def _frames_dev(frames_bytes, device):
+    return torch.from_numpy(np.frombuffer(frames_bytes, np.int64).astype(np.int32)).to(device)
+
+
+@functools.lru_cache(maxsize=16)
+def _compaction_plan(frames_bytes, T, chunk, device, by_index):
+    """Layout of the existing frames of items of frames_bytes (int64 T_b) as compacted rows, item after item, made once per distinct content:
+    row0 (B + 1,) host, rows of item b are [row0[b], row0[b + 1]); groups [(b0, b1)] of whole items of at most chunk * T rows (one item at
+    the least); on `device`: row0 (B,) and the same counted from each group's first row (what the gather of a group takes), or, by_index,
+    the (item, frame) of every row for the index gather."""
+    fr = np.frombuffer(frames_bytes, np.int64)
+    B = fr.shape[0]
+    row0 = np.concatenate(([0], np.cumsum(fr)))
+    groups, b0 = [], 0
+    while b0 < B:
+        b1 = b0 + 1
+        while b1 < B and row0[b1 + 1] - row0[b0] <= chunk * T:
+            b1 += 1
+        groups.append((b0, b1))
+        b0 = b1
+    if by_index:
+        tables = (np.repeat(np.arange(B), fr), np.concatenate([np.arange(n) for n in fr] + [np.zeros(0, np.int64)]))
+    else:
+        tables = (row0[:-1], np.concatenate([row0[a:b] - row0[a] for a, b in groups]))
+    return row0, groups, tuple(torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64)).to(device) for t in tables)
 
 
 def frames_to_pad(frame_to_pred=None, x_out=15):
@@ -112,6 +163,38 @@ def _crnn_windows_hip(feat, T, W, n_keep):
         rc = lib.disco_crnn_windows(None, feat.data_ptr(), nb, C, Tp, T, W, n_keep, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
     if rc != 0:
         raise RuntimeError(f'disco_crnn_windows failed ({rc})')
+    return out
+
+
+def _crnn_windows_rooms_hip(feat, T, W, n_keep, frames_sig, row0, n_rows):
+    """feat (nb, C, Tp, 4) contiguous float32 on the GPU, frames_sig (nb,) int32 and row0 (nb,) int64 (its exclusive prefix sum) on the
+    same device -> (n_rows, n_keep): the windows of the existing frames only, signal after signal (disco_crnn_windows_rooms)."""
+    from .. import _lib
+    lib = _lib.load()
+    nb, C, Tp, Fy = feat.shape
+    assert feat.is_contiguous() and Fy == 4 and frames_sig.dtype == torch.int32 and row0.dtype == torch.int64 and n_rows <= nb * T
+    out = torch.empty((n_rows, n_keep), dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        rc = lib.disco_crnn_windows_rooms(None, feat.data_ptr(), nb, C, Tp, T, W, n_keep, frames_sig.data_ptr(), row0.data_ptr(), out.data_ptr(),
+                                          n_rows, torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f'disco_crnn_windows_rooms failed ({rc})')
+    return out
+
+
+def _crnn_expand_rows_hip(rows, B, T, frames_sig, row0):
+    """rows (n_rows, F) contiguous float32 on the GPU -> (B, T, F): row row0[b] + t at [b, t] for t < frames_sig[b], exact zeros in the
+    frames a signal does not have (disco_crnn_expand_rows)."""
+    from .. import _lib
+    lib = _lib.load()
+    n_rows, F = rows.shape
+    assert rows.is_contiguous() and frames_sig.dtype == torch.int32 and row0.dtype == torch.int64
+    out = torch.empty((B, T, F), dtype=torch.float32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        rc = lib.disco_crnn_expand_rows(None, rows.data_ptr(), n_rows, B, T, F, frames_sig.data_ptr(), row0.data_ptr(), out.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f'disco_crnn_expand_rows failed ({rc})')
     return out
 
 
@@ -232,7 +315,7 @@ class CRNN(nn.Module):
 
     # ---- sequence evaluation
     @torch.no_grad()
-    def predict_masks(self, mag, chunk=256, frame_to_pred=PRED_FRAME, norm_type=None, compute_dtype=None, prepared=False):
+    def predict_masks(self, mag, chunk=256, frame_to_pred=PRED_FRAME, norm_type=None, compute_dtype=None, prepared=False, frames=None):
         """mag: (B, n_ch, T, F) magnitudes (un-clipped |STFT| of the node's reference mic, then |z| of the other nodes)
         -> masks (B, T, F), equal to reshape_mask(model(prepare_data(..., frame_to_pred, norm_type)), frame_to_pred) of the
         reference for every item (speech_enhancement/utils.py:13-66, 69-138; tango.py:228-240).
@@ -243,7 +326,13 @@ class CRNN(nn.Module):
         convolutions and the GRU / output GEMMs take their inputs in that type and accumulate in float32 (matrix cores at full
         rate instead of the float32 rate); the gate arithmetic, the recurrent state and the masks stay float32.  An explicit
         accuracy-for-speed switch: bench.py's C4_bf16 entry states the mask error it costs against the float32 evaluation.
-        prepared=True: `mag` is ALREADY clipped and zero-padded for `frame_to_pred` (crnn_features_hip: (B, n_ch, pad + T + pad, F)); norm_type None only."""
+        prepared=True: `mag` is ALREADY clipped and zero-padded for `frame_to_pred` (crnn_features_hip: (B, n_ch, pad + T + pad, F)); norm_type None only.
+        frames: None, or B frame counts T_b <= T (a host sequence; a tensor on a GPU is copied to the host) for items of different lengths
+        in one rectangular batch: item b comes out as `predict_masks(mag[b:b + 1, :, :T_b])` does, with exact zeros at t >= T_b.  The rows
+        t >= T_b are zeroed after the clamp (prepared=True: the caller did, crnn_features_hip(..., frames=...)), so that the convolutions, which
+        have no padding along time, see what the item's own zero padding would hold; the window gather, the GRU steps and the output layer
+        then run on the sum(T_b) existing frames only.  norm_type must be None with frames: no caller needs the per-frequency statistics
+        over a ragged batch, and they would have to be taken over every item's own frames."""
         if self.training:
             raise RuntimeError('predict_masks is the inference path (BatchNorm folded on its running statistics): call model.eval() first')
         B, C, T, F = mag.shape
@@ -261,7 +350,13 @@ class CRNN(nn.Module):
             steps = W
         else:
             raise ValueError(":param output_frames: should be 'mid' or 'last' ('all' is not implemented in the reference either)")
+        if frames is not None:
+            if norm_type is not None:
+                raise ValueError('frames (items of different lengths) with a norm_type: the statistics over a ragged batch are not offered')
+            fr, fr_dev = _frames_on(frames, B, T, mag.device)
         x = mag if prepared else torch.clamp(mag, STFT_MIN, STFT_MAX)      # normalization(): clip first, whatever the type
+        if frames is not None and not prepared:                          # the frames an item does not have: zeros, as its own padding would be
+            x = x.masked_fill((torch.arange(T, device=mag.device) >= fr_dev.view(B, 1))[:, None, :, None], 0.0)
         if norm_type == 'scale_to_unit_norm':
             x = x / torch.linalg.vector_norm(x, dim=2, keepdim=True)
         elif norm_type == 'scale_to_1':
@@ -296,23 +391,18 @@ class CRNN(nn.Module):
 
             def gemm(bias, a, wt):
                 return torch.addmm(bias, a, wt)
-        out = torch.empty((B, T, F), dtype=mag.dtype, device=mag.device)
         feat = feat.contiguous()
         sB, sC = feat.stride(0), feat.stride(1)
-        for b0 in range(0, B, chunk):
-            nb = min(chunk, B - b0)
-            # window i of channel c = frames i .. i+14 of that channel = W * Fy CONTIGUOUS floats starting at i * Fy: an
-            # overlapping strided view, gathered into rows (c, w, fy) with 60-float runs (a permuted unfold of the same
-            # data copies element by element and was the slowest kernel of the whole step)
-            if feat.is_cuda and feat.dtype == torch.float32 and Fy == 4:
-                seq = _crnn_windows_hip(feat[b0:b0 + nb], T, W, steps * Cc * Fy).view(nb * T, steps, Cc * Fy)
-            else:
-                win = feat[b0:b0 + nb].as_strided((nb, T, c_used, W * Fy), (sB, Fy, sC, 1)).reshape(nb * T, c_used * W * Fy)
-                seq = win[:, :steps * Cc * Fy].view(nb * T, steps, Cc * Fy)
-            # The GRU over `steps` steps from a zero state, for all nb * T windows at once, as plain GEMMs: one for the input
+        n_keep = steps * Cc * Fy
+        hip = feat.is_cuda and feat.dtype == torch.float32 and Fy == 4
+
+        def gru_ff(seq):
+            """seq (n, steps, Cc Fy): the windows' leading GRU inputs -> (n, F) masks of the selected output frame"""
+            # The GRU over `steps` steps from a zero state, for all n windows at once, as plain GEMMs: one for the input
             # projections of every step, one per step for the recurrent part (torch's / MIOpen's nn.GRU kernel is an order of
             # magnitude slower on this shape: a quarter of a million 8-step sequences).  Gate order r, z, n; same arithmetic.
-            gi = gemm(b_ih, seq.reshape(-1, Cc * Fy), w_ih_t).view(nb * T, steps, 3 * H)
+            n = seq.shape[0]
+            gi = gemm(b_ih, seq.reshape(-1, Cc * Fy), w_ih_t).view(n, steps, 3 * H)
             fused = gi.is_cuda and gi.dtype == torch.float32          # pointwise gate math in one HIP kernel (libdisco_hip.so)
             h = None
             for st in range(steps):
@@ -321,12 +411,59 @@ class CRNN(nn.Module):
                     gh = None if h is None else gemm(b_hh, h, w_hh_t)
                     h = _gru_gates_hip(g, gh, b_hh, h, H)
                     continue
-                gh = b_hh.expand(nb * T, -1) if h is None else gemm(b_hh, h, w_hh_t)
+                gh = b_hh.expand(n, -1) if h is None else gemm(b_hh, h, w_hh_t)
                 r = torch.sigmoid(g[:, :H] + gh[:, :H])
                 zg = torch.sigmoid(g[:, H:2 * H] + gh[:, H:2 * H])
                 nn_ = torch.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:])
                 h = (1 - zg) * nn_ if h is None else torch.addcmul((1 - zg) * nn_, zg, h)
-            out[b0:b0 + chunk] = self.ff(h).view(nb, T, F)
+            return self.ff(h)
+
+        if frames is not None:
+            return self._masks_of_existing_frames(feat, fr, fr_dev, T, F, chunk, c_used, n_keep, hip, gru_ff, mag.dtype)
+        out = torch.empty((B, T, F), dtype=mag.dtype, device=mag.device)
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            # window i of channel c = frames i .. i+14 of that channel = W * Fy CONTIGUOUS floats starting at i * Fy: an
+            # overlapping strided view, gathered into rows (c, w, fy) with 60-float runs (a permuted unfold of the same
+            # data copies element by element and was the slowest kernel of the whole step)
+            if hip:
+                seq = _crnn_windows_hip(feat[b0:b0 + nb], T, W, n_keep).view(nb * T, steps, Cc * Fy)
+            else:
+                win = feat[b0:b0 + nb].as_strided((nb, T, c_used, W * Fy), (sB, Fy, sC, 1)).reshape(nb * T, c_used * W * Fy)
+                seq = win[:, :n_keep].view(nb * T, steps, Cc * Fy)
+            out[b0:b0 + chunk] = gru_ff(seq).view(nb, T, F)
+        return out
+
+    def _masks_of_existing_frames(self, feat, fr, fr_dev, T, F, chunk, c_used, n_keep, hip, gru_ff, dtype):
+        """predict_masks' second half for items of different lengths: the recurrent layer and the output layer on the sum(fr) existing frames,
+        compacted item after item (row0 = exclusive prefix sum of fr), in groups of whole items of at most chunk * T rows -- the input
+        projections of a group are as large as those of `chunk` full items -- and the rows put back at [b, t] with zeros beyond fr[b]."""
+        B, Cc, _, Fy = feat.shape
+        W, dev = self.x_out, feat.device
+        steps = n_keep // (Cc * Fy)
+        row0, groups, tables = _compaction_plan(fr.tobytes(), T, chunk, dev, not hip)
+        N = int(row0[-1])
+        if N == 0:
+            return torch.zeros((B, T, F), dtype=dtype, device=dev)
+        rows = torch.empty((N, F), dtype=torch.float32 if hip else dtype, device=dev)
+        if hip:
+            row0_dev, rel_dev = tables                              # rel: every group's rows count from its own buffer's start
+        else:
+            b_idx, t_idx = tables
+            win = feat.as_strided((B, T, c_used, W * Fy), (feat.stride(0), Fy, feat.stride(1), 1))
+        for a, b in groups:
+            r0, r1 = int(row0[a]), int(row0[b])
+            if r1 == r0:
+                continue
+            if hip:
+                seq = _crnn_windows_rooms_hip(feat[a:b], T, W, n_keep, fr_dev[a:b], rel_dev[a:b], r1 - r0)
+            else:                                                   # the same rows by index: window t of item b, its leading n_keep floats
+                seq = win[b_idx[r0:r1], t_idx[r0:r1]].reshape(r1 - r0, c_used * W * Fy)[:, :n_keep]
+            rows[r0:r1] = gru_ff(seq.reshape(r1 - r0, steps, Cc * Fy))
+        if hip:
+            return _crnn_expand_rows_hip(rows, B, T, fr_dev, row0_dev).to(dtype)
+        out = torch.zeros((B, T, F), dtype=dtype, device=dev)
+        out[b_idx, t_idx] = rows
         return out
 
 

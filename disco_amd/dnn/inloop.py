@@ -24,6 +24,9 @@ def tango_enhance_dnn(eng, y, model_z, model_w=None, want_masks=False, dnn_chunk
     masks: optional (mask_z, mask_w) float32 (R, K, T, F) tensors used INSTEAD of the networks' predictions (the same kernel sequence on
     given masks: how bench.py re-derives the spectra of a timed step).  want_yf: the filtered spectra (R, K, T, F) complex64 come back
     as the last element; the final filter and the iSTFT then run as two calls (the one-pass kernel keeps yf on chip).
+    Per-room clip lengths (eng.set_lengths): both networks see every room as if it were alone at its own length -- the features of the frames
+    t >= T_r a room does not have are exact zeros (crnn_features_hip(..., frames=...)), the recurrent and output layers run on the existing
+    frames only (predict_masks(..., frames=...)) -- the returned masks are zero at t >= T_r and `out` is zero at and beyond L_r.
     Returns out (R, K, L) torch float32 [, mask_z, mask_w (R, K, T, F)][, yf]."""
     mark = mark or (lambda name: None)
     lib, ctx = eng.lib, eng.ctx
@@ -36,12 +39,15 @@ def tango_enhance_dnn(eng, y, model_z, model_w=None, want_masks=False, dnn_chunk
     mark('stft')
     Xc = _c64(X)                                                       # (R, K, T, F, M) complex64 view
     ref = eng.cfg.ref_mic
+    # rooms of different clip lengths: T_r per room for the features, per signal (room, node) for the networks; None = the uniform batch
+    fr_room = None if eng._lengths is None else eng.frames
+    fr_sig = {} if fr_room is None else {'frames': np.repeat(fr_room, K)}
     if masks is not None:
         mask_z = masks[0].contiguous()
     else:
         # |Y| at the reference mic (tango.py:338), clipped and padded for the window selection (prepare_data) in one pass
-        feat = crnn_features_hip(Xc, None, ref, frames_to_pad(None, model_z.x_out))
-        mask_z = model_z.predict_masks(feat, chunk=dnn_chunk, compute_dtype=compute_dtype, prepared=True).reshape(R, K, T, F).contiguous()
+        feat = crnn_features_hip(Xc, None, ref, frames_to_pad(None, model_z.x_out), frames=fr_room)
+        mask_z = model_z.predict_masks(feat, chunk=dnn_chunk, compute_dtype=compute_dtype, prepared=True, **fr_sig).reshape(R, K, T, F).contiguous()
         del feat
     mark('crnn_z')
     eng._chk(lib.disco_cov_masked(ctx, p(X), p(mask_z), None, None, 0, M, None, None, None))
@@ -58,8 +64,8 @@ def tango_enhance_dnn(eng, y, model_z, model_w=None, want_masks=False, dnn_chunk
         eng._chk(lib.disco_apply(ctx, p(X), None, p(w_loc), M, 1, p(z), None))
         mark('apply1')
         # step 2 always looks at channel 0 (tango.py:391), then the |z| of the other nodes in node order (get_z_for_mask 'zs_hat', :158-186)
-        feat = crnn_features_hip(Xc, _c64(z), 0, frames_to_pad(None, model_w.x_out))
-        mask_w = model_w.predict_masks(feat, chunk=dnn_chunk, compute_dtype=compute_dtype, prepared=True).reshape(R, K, T, F).contiguous()
+        feat = crnn_features_hip(Xc, _c64(z), 0, frames_to_pad(None, model_w.x_out), frames=fr_room)
+        mask_w = model_w.predict_masks(feat, chunk=dnn_chunk, compute_dtype=compute_dtype, prepared=True, **fr_sig).reshape(R, K, T, F).contiguous()
         del feat
         mark('crnn_w')
     out = torch.empty((R, K, L), dtype=torch.float32, device=dev)

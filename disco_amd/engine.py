@@ -428,7 +428,8 @@ class Engine:
         """Per-room clip lengths (disco_set_lengths): `lengths` holds one valid length L_r <= length per room, or is None to restore
         the uniform batch.  The arrays keep their shapes; room r is processed as if run alone in an engine of length L_r: samples at
         and beyond L_r are never read, frames t >= T_r = 1 + L_r / hop are exact zeros in every spectrum and computed mask, output
-        samples at and beyond L_r are exact zeros.  Masks passed in must be finite in the padding frames.  The online mode,
+        samples at and beyond L_r are exact zeros.  Masks passed in must be finite in the padding frames.  CRNN masks follow the lengths
+        (dnn/inloop.py:tango_enhance_dnn, CRNN.predict_masks(..., frames=self.frames repeated per node)).  The online mode,
         `mask_ivad` and a node shard refuse while lengths are set."""
         if lengths is None:
             self._chk(self.lib.disco_set_lengths(self.ctx, None, 0))

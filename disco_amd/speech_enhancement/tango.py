@@ -69,7 +69,8 @@ def _get_mask(eng, Sh_c, Nh_c, ts, vad, mod=None, Yh_c=None, z_rows=None):
 def _time_mask(eng, vad, s_ch, n_ch, y_ch=None, mod=None, z_rows=None, n_fft=N_FFT, pad_mode='reflect', lengths=None):
     """A mask the library does not compute by itself inside disco_tango_reference, as a device array (R, K, T, F):
     'ivad' (frame VAD of the target image's time signal, tango.py:217-221), a TF mask of ANOTHER type than the engine's
-    (step 2 with vads[1] != vads[0]), or the CRNN's prediction from |STFT(y_ch)| [+ |z| of the other nodes]."""
+    (step 2 with vads[1] != vads[0]), or the CRNN's prediction from |STFT(y_ch)| [+ |z| of the other nodes].
+    lengths (the engine's, when set): the other-type TF mask and the CRNN take every room at its own length."""
     R, K, L = s_ch.shape
     if vad == 'ivad':
         return eng.mask_ivad(np.ascontiguousarray(s_ch.reshape(R * K, L))).reshape(R, K, eng.T, eng.F)
@@ -81,7 +82,8 @@ def _time_mask(eng, vad, s_ch, n_ch, y_ch=None, mod=None, z_rows=None, n_fft=N_F
             mag = np.concatenate([mag, np.abs(z_rows).reshape(R * K, -1, eng.T, eng.F)], axis=1)
         par = next(mod.parameters())
         with torch.no_grad():
-            m = mod.predict_masks(torch.from_numpy(np.ascontiguousarray(mag)).to(par.device, par.dtype))
+            m = mod.predict_masks(torch.from_numpy(np.ascontiguousarray(mag)).to(par.device, par.dtype),
+                                  frames=None if lengths is None else np.repeat(eng.frames, K))
         return np.ascontiguousarray(m.float().cpu().numpy().reshape(R, K, eng.T, eng.F))
     other = get_engine(rooms=R, nodes=K, mics=1, length=L, n_fft=n_fft, mask=vad, pad_mode=pad_mode)
     try:                                                                       # (a cached engine: the lengths do not outlive the call)
@@ -99,10 +101,11 @@ def offline_tango_batched(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_
     The whole path is ONE library call (disco_tango_reference: STFTs, masks, statistics, solves, every mask_for_z variant and
     the three filter passes stay on the device); only 'ivad' / DNN masks are prepared outside it and passed in.
     lengths: (R,) valid samples per room (Engine.set_lengths): room r comes out as if it had been run alone at L = lengths[r]; the
-    frames beyond its T_r = 1 + lengths[r] / hop are zeros in every returned array.  TF mask types only."""
+    frames beyond its T_r = 1 + lengths[r] / hop are zeros in every returned array.  TF mask types and 'crnn' (at either step) take
+    lengths; 'ivad' does not."""
     vads = _mask_names(vads, mods)
-    if lengths is not None and any(v in ('ivad', 'crnn') for v in vads):
-        raise NotImplementedError("per-room lengths with 'ivad' / 'crnn' masks: only the TF mask types take lengths")
+    if lengths is not None and 'ivad' in vads:
+        raise NotImplementedError("per-room lengths with 'ivad' masks: only the TF mask types and 'crnn' take lengths")
     mods = [None, None] if mods is None else list(mods) + [None] * (2 - len(mods))
     MODES = ('local', None, 'distant', 'compressed', 'use_oracle_refs', 'use_oracle_zs', 'previous')
     if mask_for_z not in MODES:
@@ -129,7 +132,7 @@ def _tango_batched_on(eng, y, s, n, vads, mods, mask_for_z, z_sigs, n_fft, pad_m
     tf = lambda v: v[:-1] in ('irm', 'ibm', 'iam')
     # masks the library cannot derive from (S, N) with the engine's own TF type (see _time_mask); None = computed inside
     mz = None if tf(vads[0]) else _time_mask(eng, vads[0], s[:, :, ref_mic], n[:, :, ref_mic], y[:, :, ref_mic], mods[0],
-                                             n_fft=n_fft, pad_mode=pad_mode)
+                                             n_fft=n_fft, pad_mode=pad_mode, lengths=lengths)
     yd, sd, nd = eng.to_device(y, np.float32)[1], eng.to_device(s, np.float32)[1], eng.to_device(n, np.float32)[1]
     need_z_for_mw = vads[1] == 'crnn' and mods[1] is not None
     if steps == 1 or need_z_for_mw:
@@ -143,7 +146,7 @@ def _tango_batched_on(eng, y, s, n, vads, mods, mask_for_z, z_sigs, n_fft, pad_m
             from ..dnn.crnn import get_z_for_mask
             rows = np.stack([np.stack([get_z_for_mask(out['z_y'][r], out['zn'][r], k, K, z_sigs) for k in range(K)])
                              for r in range(R)]) if K > 1 else None
-            mw = _time_mask(eng, 'crnn', s[:, :, 0], n[:, :, 0], y[:, :, 0], mods[1], rows, n_fft=n_fft, pad_mode=pad_mode)
+            mw = _time_mask(eng, 'crnn', s[:, :, 0], n[:, :, 0], y[:, :, 0], mods[1], rows, n_fft=n_fft, pad_mode=pad_mode, lengths=lengths)
     elif tf(vads[1]) and tf(vads[0]) and vads[1] == vads[0]:
         mw = None                                                              # the library's own tf_mask at channel 0
     elif vads[1] == vads[0] and ref_mic == 0:
@@ -258,11 +261,12 @@ def offline_tango(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_sigs='zs
     return tuple([np.ascontiguousarray(d[nm][0, k].T) for k in range(K)] for nm in names)
 
 
-def offline_tango_rooms(rooms, vads='irm1', mask_for_z=MASK_Z, n_fft=N_FFT, pad_mode='reflect', ref_mic=0, mu=1.0):
+def offline_tango_rooms(rooms, vads='irm1', mask_for_z=MASK_Z, n_fft=N_FFT, pad_mode='reflect', ref_mic=0, mu=1.0, mods=None, z_sigs='zs_hat'):
     """`offline_tango` for a list of rooms whose clips differ in length, in ONE batched call: `rooms` is a list of (y, s, n), each in
     the reference's [node][channel] -> time form, all with the same node and channel counts.  Returns a list with the reference's
     9-tuple of every room, (yf, sf, nf, z_y, z_s, z_n, zn, masks_z, mask_w), each a list over nodes of (F, T_r) arrays with
-    T_r = 1 + L_r / hop: what `offline_tango` returns for that room alone."""
+    T_r = 1 + L_r / hop: what `offline_tango` returns for that room alone.  vads: TF mask types or 'crnn' (models in `mods`, the step-2
+    network's compressed inputs chosen by `z_sigs`, as in `offline_tango`)."""
     names = ['yf', 'sf', 'nf', 'z_y', 'z_s', 'z_n', 'zn', 'masks_z', 'mask_w']
     trip = []
     for r, room in enumerate(rooms):
@@ -281,7 +285,7 @@ def offline_tango_rooms(rooms, vads='irm1', mask_for_z=MASK_Z, n_fft=N_FFT, pad_
     for r, b in enumerate(trip):
         for i in range(3):
             ysn[i, r, :, :, :lengths[r]] = b[i][0]
-    d = offline_tango_batched(ysn[0], ysn[1], ysn[2], vads=vads, mask_for_z=mask_for_z, n_fft=n_fft, pad_mode=pad_mode, ref_mic=ref_mic,
-                              mu=mu, lengths=lengths)
+    d = offline_tango_batched(ysn[0], ysn[1], ysn[2], vads=vads, mods=mods, mask_for_z=mask_for_z, z_sigs=z_sigs, n_fft=n_fft, pad_mode=pad_mode,
+                              ref_mic=ref_mic, mu=mu, lengths=lengths)
     frames = 1 + lengths // (n_fft // 2)
     return [tuple([np.ascontiguousarray(d[nm][r, k, :frames[r]].T) for k in range(K)] for nm in names) for r in range(R)]

@@ -493,12 +493,30 @@ int disco_conv3x3_pool4(disco_ctx* ctx, const float* x, const float* w, const fl
 int disco_crnn_features(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, int64_t R, int K, int M, int T, int F, int mic, int pad_lo, int pad_hi,
                         float lo, float hi, float* out, disco_stream s);
 
+/* disco_crnn_features for a batch whose rooms differ in clip length (disco_set_lengths): frames [R] (device) holds T_r = 1 + L_r / hop <= T.  Rows
+ * pad_lo + t with t < T_r hold the bits disco_crnn_features writes; every row with t >= T_r is an exact 0.f like the padding rows -- NOT clipped up to
+ * `lo`: the reference pads zeros after the clip, which is what the room run alone at T_r sees there -- in channel 0 and in the |z| channels alike;
+ * X and Z are not read there.  ctx may be NULL. */
+int disco_crnn_features_rooms(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, int64_t R, int K, int M, int T, int F, int mic, int pad_lo,
+                              int pad_hi, float lo, float hi, const int32_t* frames, float* out, disco_stream s);
+
 /* The recurrent layer's input windows: the reference re-interprets every 15-frame window of the (C, frames, 4) feature map as a
  * (15, 256) sequence WITHOUT a transpose (dnn/models/crnn.py:59), so window t is the flattened block feat[:, t : t + W, :];
  * out[(b T + t)][0 : n_keep] = its leading n_keep floats (n_keep = 256 x GRU steps actually run, a multiple of 4).
  * feat [B][C][Tp][4] float, Tp >= T + W - 1; feat and out 16-byte aligned.  ctx may be NULL. */
 int disco_crnn_windows(disco_ctx* ctx, const float* feat, int64_t B, int C, int Tp, int T, int W, int n_keep, float* out,
                        disco_stream s);
+
+/* disco_crnn_windows for signals of different frame counts, compacted: signal b has frames_sig[b] <= T frames (device, [B]) and row0[b] (device, [B]) is
+ * the exclusive prefix sum of frames_sig; out [n_rows][n_keep], row row0[b] + t (t < frames_sig[b]) = the bytes disco_crnn_windows writes to row
+ * b T + t.  Nothing else is written; a row outside [0, n_rows) is skipped.  Same alignment and argument rules as disco_crnn_windows.  ctx may be NULL. */
+int disco_crnn_windows_rooms(disco_ctx* ctx, const float* feat, int64_t B, int C, int Tp, int T, int W, int n_keep, const int32_t* frames_sig,
+                             const int64_t* row0, float* out, int64_t n_rows, disco_stream s);
+
+/* The inverse placement, for the output layer's rows: out [B][T][F], out[b][t] = rows[row0[b] + t] for t < frames_sig[b], exact zeros for the frames a
+ * signal does not have; rows [n_rows][F].  One pass that writes EVERY element of out (16-byte stores when out is 16-byte aligned).  ctx may be NULL. */
+int disco_crnn_expand_rows(disco_ctx* ctx, const float* rows, int64_t n_rows, int64_t B, int T, int F, const int32_t* frames_sig, const int64_t* row0,
+                           float* out, disco_stream s);
 
 /* ---- evaluation metrics right after the path --------------------------------------------------
  * Raw float64 moments behind disco_theque/metrics.py; the dB / clipping / weighting of a handful of numbers per signal
