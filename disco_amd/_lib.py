@@ -91,10 +91,15 @@ PROTOTYPES = {
     'disco_pair_stats': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     'disco_band_stats': (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _int, _vp, _vp]),
     'disco_band_stats_gated': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _int, _vp, _vp]),
+    'disco_pair_stats_spans': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
+    'disco_band_stats_spans': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp]),
     'disco_lag_corr_workspace_bytes': (_sz, [_vp, _i64, _i64, _int]),
     'disco_lag_corr': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _sz, _vp]),
+    'disco_lag_corr_spans': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _vp, _vp, _sz, _vp]),
     'disco_bss_workspace_bytes': (_sz, [_vp, _i64, _int, _int, _i64]),
     'disco_bss_eval': (_int, [_vp, _vp, _vp, _i64, _int, _int, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    'disco_bss_eval_spans': (_int, [_vp, _vp, _vp, _i64, _int, _int, _i64, _int, _vp, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    'disco_bss_estimates': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
     'disco_stoi_workspace_bytes': (_sz, [_vp, _i64, _i64, _int, _int, _int]),
     'disco_stoi': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
     'disco_reference_workspace_bytes': (_sz, [_vp]),

@@ -162,32 +162,60 @@ extern "C" int disco_crnn_expand_rows(disco_ctx* ctx, const float* rows, int64_t
 }
 // ---- evaluation metrics ----------------------------------------------------------------------------------
 
-extern "C" int disco_pair_stats(disco_ctx* ctx, const float* a, const float* b, int64_t n_sig, int64_t len, int start, int stop,
-                                double* stats, disco_stream s) {
+// the scalar-stop entry points pass stop_sig == nullptr; the _spans ones pass stop = len (what a null array means) and the device array
+
+static int pair_stats_impl(disco_ctx* ctx, const float* a, const float* b, int64_t n_sig, int64_t len, int start, int stop, const int32_t* stop_sig,
+                           double* stats, disco_stream s) {
     DISCO_ENTER(ctx);
     if (!a || !b || !stats || n_sig < 1 || len < 1) return fail(ctx, DISCO_E_ARG, "disco_pair_stats: bad argument");
-    if (start < 0 || stop > len || stop < start) return fail(ctx, DISCO_E_ARG, "disco_pair_stats: need 0 <= start <= stop <= len");
+    if (start < 0 || stop > len || stop < start)
+        return fail(ctx, DISCO_E_ARG, stop_sig ? "disco_pair_stats: need 0 <= start <= len" : "disco_pair_stats: need 0 <= start <= stop <= len");
     if (n_sig > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_pair_stats: batch too large");
-    hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)n_sig), dim3(METRIC_THREADS), 0, (hipStream_t)s, a, b, (long long)len, start, stop, stats);
+    hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)n_sig), dim3(METRIC_THREADS), 0, (hipStream_t)s, a, b, (long long)len, start, stop,
+                       (const int*)stop_sig, stats);
     return check_launch(ctx, "k_pair_stats");
 }
 
-extern "C" int disco_band_stats_gated(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, int stop,
-                                      const double* b, const double* a, int n_bands, double* stats, disco_stream s) {
+extern "C" int disco_pair_stats(disco_ctx* ctx, const float* a, const float* b, int64_t n_sig, int64_t len, int start, int stop,
+                                double* stats, disco_stream s) {
+    return pair_stats_impl(ctx, a, b, n_sig, len, start, stop, nullptr, stats, s);
+}
+
+extern "C" int disco_pair_stats_spans(disco_ctx* ctx, const float* a, const float* b, int64_t n_sig, int64_t len, int start, const int32_t* stop,
+                                      double* stats, disco_stream s) {
+    if (ctx && len > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_pair_stats_spans: signals longer than 2^31 - 1 samples");
+    return pair_stats_impl(ctx, a, b, n_sig, len, start, (int)len, stop, stats, s);
+}
+
+static int band_stats_impl(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, int stop,
+                           const int32_t* stop_sig32, const double* b, const double* a, int n_bands, double* stats, disco_stream s) {
     DISCO_ENTER(ctx);
+    const int* stop_sig = (const int*)stop_sig32;
     if (!x || !b || !a || !stats || n_sig < 1 || len < 1) return fail(ctx, DISCO_E_ARG, "disco_band_stats: bad argument");
-    if (start < 0 || stop > len || stop < start) return fail(ctx, DISCO_E_ARG, "disco_band_stats: need 0 <= start <= stop <= len");
+    if (start < 0 || stop > len || stop < start)
+        return fail(ctx, DISCO_E_ARG, stop_sig ? "disco_band_stats: need 0 <= start <= len" : "disco_band_stats: need 0 <= start <= stop <= len");
     if (n_bands < 1 || n_bands > METRIC_THREADS) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_band_stats: 1 <= n_bands <= 256");
     const int spb = std::min(IIR_MAX_SPB, METRIC_THREADS / n_bands);
     const long long grid = (n_sig + spb - 1) / spb;
     if (grid > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_band_stats: batch too large");
     if (gate)
         hipLaunchKernelGGL(k_band_stats<true>, dim3((unsigned)grid), dim3(METRIC_THREADS), 0, (hipStream_t)s, x, gate, (long long)n_sig,
-                           (long long)len, start, stop, b, a, n_bands, spb, stats);
+                           (long long)len, start, stop, stop_sig, b, a, n_bands, spb, stats);
     else
         hipLaunchKernelGGL(k_band_stats<false>, dim3((unsigned)grid), dim3(METRIC_THREADS), 0, (hipStream_t)s, x, gate, (long long)n_sig,
-                           (long long)len, start, stop, b, a, n_bands, spb, stats);
+                           (long long)len, start, stop, stop_sig, b, a, n_bands, spb, stats);
     return check_launch(ctx, "k_band_stats");
+}
+
+extern "C" int disco_band_stats_gated(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, int stop,
+                                      const double* b, const double* a, int n_bands, double* stats, disco_stream s) {
+    return band_stats_impl(ctx, x, gate, n_sig, len, start, stop, nullptr, b, a, n_bands, stats, s);
+}
+
+extern "C" int disco_band_stats_spans(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, const int32_t* stop,
+                                      const double* b, const double* a, int n_bands, double* stats, disco_stream s) {
+    if (ctx && len > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_band_stats_spans: signals longer than 2^31 - 1 samples");
+    return band_stats_impl(ctx, x, gate, n_sig, len, start, (int)len, stop, b, a, n_bands, stats, s);
 }
 
 extern "C" int disco_band_stats(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len, int start, int stop,

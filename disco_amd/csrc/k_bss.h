@@ -12,6 +12,13 @@
 
 namespace disco {
 
+// scored end of row / set i: the launch's scalar `stop`, or stop_sig[i] clamped into [start, len] (disco_stoi's rule)
+__device__ __forceinline__ int bss_stop(const int* __restrict__ stop_sig, long long i, long long len, int start, int stop) {
+    if (!stop_sig) return stop;
+    const long long e = stop_sig[i];
+    return (int)(e < start ? start : e > len ? len : e);
+}
+
 constexpr int BSS_THREADS = 256;
 constexpr int BSS_MAX_SRC = 4;
 constexpr int BSS_MAX_FLEN = 512;
@@ -52,9 +59,11 @@ __device__ __forceinline__ void lag_rows(int mode, int nsrc, int n_est, int kest
 }
 
 // part[pair][chunk][l] = sum over the chunk's n (n and n + t inside [start, stop)) of a[n] b[n + t],  t = lag_lo + l,  l < nlag
+// stop_sig: one stop per pair (mode 0) or per reference set (modes 1, 2).  Chunk c starts at start + c LC_SPAN whatever the stop and a
+// chunk wholly past the pair's stop writes zero partials, so the sum in chunk order has the bits of a launch with that scalar stop.
 static __global__ __launch_bounds__(BSS_THREADS) void k_lag_corr(const float* __restrict__ a, const float* __restrict__ b, long long len,
-                                                                 int start, int stop, int lag_lo, int nlag, int n_chunk, int mode, int nsrc,
-                                                                 int n_est, int kest, double* __restrict__ part) {
+                                                                 int start, int stop_all, const int* __restrict__ stop_sig, int lag_lo, int nlag,
+                                                                 int n_chunk, int mode, int nsrc, int n_est, int kest, double* __restrict__ part) {
     __shared__ double As[LC_A_WORDS] __attribute__((aligned(16)));
     __shared__ double Bs[LC_B_WORDS] __attribute__((aligned(16)));
     const int tid = threadIdx.x;
@@ -62,6 +71,7 @@ static __global__ __launch_bounds__(BSS_THREADS) void k_lag_corr(const float* __
     const int chunk = (int)(blockIdx.x - pair * n_chunk);
     long long ra, rb;
     lag_rows(mode, nsrc, n_est, kest, pair, ra, rb);
+    const int stop = bss_stop(stop_sig, mode == 0 ? pair : pair / (nsrc * nsrc), len, start, stop_all);
     const float* pa = a + ra * len;
     const float* pb = b + rb * len;
     const int LG = (nlag + LC_LPT - 1) / LC_LPT;
@@ -330,8 +340,9 @@ constexpr int PJ_MAX_N = BSS_MAX_SRC * BSS_MAX_FLEN;
 
 static __global__ __launch_bounds__(BSS_THREADS) void k_bss_project(const double* __restrict__ Cd, const double* __restrict__ G, long long set_words,
                                                                     const int* __restrict__ stat, const float* __restrict__ ests, long long len,
-                                                                    int start, int stop, int nsrc, int flen, int n_est, int kest, int all_pairs,
-                                                                    double* __restrict__ out, int* __restrict__ status) {
+                                                                    int start, int stop_all, const int* __restrict__ stop_sig, int nsrc, int flen,
+                                                                    int n_est, int kest, int all_pairs, double* __restrict__ out,
+                                                                    int* __restrict__ status) {
     __shared__ double ys[PJ_RHS][PJ_MAX_N];
     __shared__ double red[PJ_RHS][CH_NB][9];
     __shared__ double rs[3 * PJ_RHS][BSS_THREADS];
@@ -342,6 +353,7 @@ static __global__ __launch_bounds__(BSS_THREADS) void k_bss_project(const double
     const long long sj = blockIdx.x / ngrp;
     const long long set = sj / nsrc;
     const int job = (int)(sj - set * nsrc);
+    const int stop = bss_stop(stop_sig, set, len, start, stop_all);
     const int i0 = grp * PJ_RHS;
     const int nr = (nsrc - i0) < PJ_RHS ? (nsrc - i0) : PJ_RHS;
     const int N = job == 0 ? nsrc * flen : flen;
@@ -446,6 +458,43 @@ static __global__ __launch_bounds__(BSS_THREADS) void k_bss_project(const double
             }
         }
         if (job == 0 && grp == 0) status[set] = b;
+    }
+}
+
+// ---- the estimate sets of a room's nodes ------------------------------------------------------------------------------------------
+// The three estimate sets the reference scores per node (tango.py:547-549) from the mixture y, the step-2 output sh and the step-1
+// output szh, rows [n_sig][len]:  ests[sig][3][2][len] = {sh, y - sh}, {szh, y - szh}, {y, y - sh}, each difference formed in float64
+// and rounded to float32 once.  Samples outside [start, stop of the signal) are written as exact zeros and not read.  A workgroup
+// walks tiles of (signal, BE_TILE consecutive samples): every load and store of a wave covers 64 consecutive floats.
+constexpr int BE_TILE = 4 * BSS_THREADS;
+
+static __global__ __launch_bounds__(BSS_THREADS) void k_bss_estimates(const float* __restrict__ y, const float* __restrict__ sh,
+                                                                      const float* __restrict__ szh, long long n_sig, long long len, int start,
+                                                                      int stop_all, const int* __restrict__ stop_sig, float* __restrict__ ests) {
+    const long long tiles_per_sig = (len + BE_TILE - 1) / BE_TILE, n_tile = n_sig * tiles_per_sig;
+    for (long long tile = blockIdx.x; tile < n_tile; tile += gridDim.x) {
+        const long long sig = tile / tiles_per_sig;
+        const long long n0 = (tile - sig * tiles_per_sig) * BE_TILE;
+        const int stop = bss_stop(stop_sig, sig, len, start, stop_all);
+        const float *py = y + sig * len, *ps = sh + sig * len, *pz = szh + sig * len;
+        float* o = ests + sig * 6 * len;
+#pragma unroll
+        for (int u = 0; u < BE_TILE / BSS_THREADS; ++u) {
+            const long long n = n0 + u * BSS_THREADS + threadIdx.x;
+            if (n >= len) break;
+            float vy = 0.f, vs = 0.f, vz = 0.f, dys = 0.f, dyz = 0.f;
+            if (n >= start && n < stop) {
+                vy = py[n], vs = ps[n], vz = pz[n];
+                dys = (float)((double)vy - (double)vs);
+                dyz = (float)((double)vy - (double)vz);
+            }
+            o[n] = vs;
+            o[len + n] = dys;
+            o[2 * len + n] = vz;
+            o[3 * len + n] = dyz;
+            o[4 * len + n] = vy;
+            o[5 * len + n] = dys;
+        }
     }
 }
 

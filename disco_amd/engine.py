@@ -201,22 +201,41 @@ class Engine:
         return out
 
     # ---- evaluation metrics (disco_theque/metrics.py)
+    def _span_stops(self, stop, n, L, start):
+        """`stop` of a metric call -> (scalar stop, None) for None / a scalar, or (None, (device pointer, keep-alive)) for an (n,) array:
+        one stop per signal, validated on the host and uploaded once (the `_spans` entry points)."""
+        if stop is None or not np.ndim(stop):
+            return (L if stop is None else int(stop)), None
+        stops = np.asarray(stop)
+        if stops.shape != (n,):
+            raise ValueError(f'stop must be None, a scalar or an ({n},) array, one entry per signal: got shape {stops.shape}')
+        if not np.issubdtype(stops.dtype, np.integer):
+            raise ValueError(f'stop must hold integers, got {stops.dtype}')
+        if int(start) < 0 or np.any(stops < start) or np.any(stops > L):
+            raise ValueError(f'need 0 <= start <= stop <= L = {L}: start {start}, stop {stop}')
+        return None, self.to_device(np.ascontiguousarray(stops, dtype=np.int32), np.int32)
+
     def pair_stats(self, a, b, start=0, stop=None):
         """a, b (n_sig, L) float32 -> (n_sig, 8) float64 moments of a[:, start:stop], b[:, start:stop]
-        {#(a!=0), sum a, sum a^2, #(b!=0), sum b, sum b^2, sum ab, n}."""
+        {#(a!=0), sum a, sum a^2, #(b!=0), sum b, sum b^2, sum ab, n}.  stop: None (L), a scalar, or an (n_sig,) array -- signal i is
+        then scored over [start, stop[i]) and nothing at or beyond stop[i] is read (disco_pair_stats_spans)."""
         n_sig, L = a.shape
-        stop = L if stop is None else stop
+        stop, dstop = self._span_stops(stop, n_sig, L, start)
         pa, ka = self.to_device(a, np.float32)
         pb, kb = (pa, ka) if b is a else self.to_device(b, np.float32)
         st = self.empty((n_sig, 8), np.float64)
-        self._chk(self.lib.disco_pair_stats(self.ctx, pa, pb, n_sig, L, start, stop, st.ptr, self.stream))
+        if dstop is not None:
+            self._chk(self.lib.disco_pair_stats_spans(self.ctx, pa, pb, n_sig, L, start, dstop[0], st.ptr, self.stream))
+        else:
+            self._chk(self.lib.disco_pair_stats(self.ctx, pa, pb, n_sig, L, start, stop, st.ptr, self.stream))
         return st
 
     def band_stats(self, x, b, a, start=0, stop=None, gate=None):
         """x (n_sig, L) float32; b, a (n_bands, 9) float64 -> (n_sig, n_bands, 3) float64 {#(y!=0), sum y, sum y^2} of
-        y = lfilter(b_j, a_j, x[:, start:stop]); gate (n_sig, L) float32: the samples with gate != 0 instead of those with y != 0."""
+        y = lfilter(b_j, a_j, x[:, start:stop]); gate (n_sig, L) float32: the samples with gate != 0 instead of those with y != 0.
+        stop: None (L), a scalar, or an (n_sig,) array -- signal i is filtered and scored over [start, stop[i]) (disco_band_stats_spans)."""
         n_sig, L = x.shape
-        stop = L if stop is None else stop
+        stop, dstop = self._span_stops(stop, n_sig, L, start)
         b = np.ascontiguousarray(b, np.float64)
         a = np.ascontiguousarray(a, np.float64)
         assert b.shape == a.shape and b.shape[1] == 9, 'order-4 band-pass (9 coefficients per polynomial) expected'
@@ -224,9 +243,13 @@ class Engine:
         pb, kb = self.to_device(b, np.float64)
         pa, ka = self.to_device(a, np.float64)
         st = self.empty((n_sig, b.shape[0], 3), np.float64)
+        pg = kg = None
         if gate is not None:
             assert tuple(gate.shape) == (n_sig, L), 'the gate is indexed like the signals'
             pg, kg = self.to_device(gate, np.float32)
+        if dstop is not None:
+            self._chk(self.lib.disco_band_stats_spans(self.ctx, px, pg, n_sig, L, start, dstop[0], pb, pa, b.shape[0], st.ptr, self.stream))
+        elif gate is not None:
             self._chk(self.lib.disco_band_stats_gated(self.ctx, px, pg, n_sig, L, start, stop, pb, pa, b.shape[0], st.ptr, self.stream))
         else:
             self._chk(self.lib.disco_band_stats(self.ctx, px, n_sig, L, start, stop, pb, pa, b.shape[0], st.ptr, self.stream))
@@ -234,18 +257,23 @@ class Engine:
 
     def lag_corr(self, a, b, lag_lo, lag_hi, start=0, stop=None):
         """a, b (n_pair, L) float32 -> (n_pair, lag_hi - lag_lo + 1) float64: c[i][t - lag_lo] = sum_n a[i][n] b[i][n + t] over the n with
-        n and n + t inside [start, stop); lags within +-511  (disco_lag_corr)."""
+        n and n + t inside [start, stop); lags within +-511  (disco_lag_corr).  stop: None (L), a scalar, or an (n_pair,) array -- pair i
+        then counts as zero outside [start, stop[i]) and is not read there (disco_lag_corr_spans)."""
         if len(a.shape) != 2 or tuple(a.shape) != tuple(b.shape):
             raise ValueError(f'a and b must both be (n_pair, L): {tuple(a.shape)} and {tuple(b.shape)}')
         n_pair, L = (int(v) for v in a.shape)
-        stop = L if stop is None else stop
+        stop, dstop = self._span_stops(stop, n_pair, L, start)
         nlag = int(lag_hi) - int(lag_lo) + 1
         pa, ka = self.to_device(a, np.float32)
         pb, kb = (pa, ka) if b is a else self.to_device(b, np.float32)
         wsb = int(self.lib.disco_lag_corr_workspace_bytes(self.ctx, n_pair, L, max(nlag, 1)))
         ws = self.empty((max(wsb, 8) // 8,), np.float64)
         out = self.empty((n_pair, max(nlag, 1)), np.float64)
-        self._chk(self.lib.disco_lag_corr(self.ctx, pa, pb, n_pair, L, start, stop, lag_lo, lag_hi, out.ptr, ws.ptr, ws.nbytes, self.stream))
+        if dstop is not None:
+            self._chk(self.lib.disco_lag_corr_spans(self.ctx, pa, pb, n_pair, L, start, dstop[0], lag_lo, lag_hi, out.ptr, ws.ptr, ws.nbytes,
+                                                    self.stream))
+        else:
+            self._chk(self.lib.disco_lag_corr(self.ctx, pa, pb, n_pair, L, start, stop, lag_lo, lag_hi, out.ptr, ws.ptr, ws.nbytes, self.stream))
         return out
 
     BSS_WORKSPACE_BUDGET = 1 << 30      # bytes of factor / correlation workspace one disco_bss_eval call of Engine.bss_eval may take
@@ -256,7 +284,9 @@ class Engine:
         source j -- each {p_j, p_all, ee, status}; status (n_set,) int32, non-zero where the set's Gram matrix is singular to working
         precision (its energies are NaN).  A large batch is walked in chunks of sets whose workspace stays under `budget_bytes` (default
         BSS_WORKSPACE_BUDGET; 10 MB of factors per two-source set at flen 512, so about 100 sets per chunk); the chunking does not
-        change a bit of the result.  NumPy inputs are copied chunk by chunk; device-resident tensors / DevBufs are read in place."""
+        change a bit of the result.  NumPy inputs are copied chunk by chunk; device-resident tensors / DevBufs are read in place.
+        stop: None (L), a scalar, or an (n_set,) array -- set i, references and estimates, is then scored over [start, stop[i]) and not
+        read outside it (disco_bss_eval_spans); the array is uploaded once and walked along with the sets."""
         rs, es = tuple(int(v) for v in refs.shape), tuple(int(v) for v in ests.shape)
         if len(rs) != 3 or len(es) != 4 or es[0] != rs[0] or es[2:] != rs[1:]:
             raise ValueError(f'refs must be (n_set, nsrc, L) and ests (n_set, n_est, nsrc, L): {rs} and {es}')
@@ -264,11 +294,12 @@ class Engine:
         n_est = es[1]
         if min(n_set, nsrc, L, n_est) < 1:
             raise ValueError(f'empty batch: refs {rs}, ests {es}')
-        stop = L if stop is None else stop
+        stop, dstop = self._span_stops(stop, n_set, L, start)
         flen = int(flen)
         per_set = int(self.lib.disco_bss_workspace_bytes(self.ctx, 1, nsrc, flen, L))
         if per_set == 0:                                  # outside the supported range: the library names the limit, nothing is launched
-            self._chk(self.lib.disco_bss_eval(self.ctx, None, None, n_set, nsrc, n_est, L, start, stop, flen, int(all_pairs), None, None, None, 0, self.stream))
+            self._chk(self.lib.disco_bss_eval(self.ctx, None, None, n_set, nsrc, n_est, L, start, L if stop is None else stop, flen, int(all_pairs),
+                                              None, None, None, 0, self.stream))
             raise DiscoError('disco_bss_eval: unsupported shape')
         budget = self.BSS_WORKSPACE_BUDGET if budget_bytes is None else int(budget_bytes)
         step = max(1, min(n_set, budget // per_set))
@@ -295,11 +326,42 @@ class Engine:
                 pe = pe0 + 4 * i0 * n_est * nsrc * L
             out = self.empty((n, n_est) + oshape, np.float64)
             st = self.empty((n,), np.int32)
-            self._chk(self.lib.disco_bss_eval(self.ctx, pr, pe, n, nsrc, n_est, L, start, stop, flen, int(all_pairs), out.ptr, st.ptr, ws.ptr,
-                                              ws.nbytes, self.stream))
+            if dstop is not None:
+                self._chk(self.lib.disco_bss_eval_spans(self.ctx, pr, pe, n, nsrc, n_est, L, start, dstop[0] + 4 * i0, flen, int(all_pairs), out.ptr,
+                                                        st.ptr, ws.ptr, ws.nbytes, self.stream))
+            else:
+                self._chk(self.lib.disco_bss_eval(self.ctx, pr, pe, n, nsrc, n_est, L, start, stop, flen, int(all_pairs), out.ptr, st.ptr, ws.ptr,
+                                                  ws.nbytes, self.stream))
             energies[i0:i0 + n] = out.numpy()
             status[i0:i0 + n] = st.numpy()
         return energies, status
+
+    def bss_estimates(self, y, sh, szh, start=0, stop=None, out=None):
+        """The three estimate sets tango.py:547-549 scores per node (disco_bss_estimates): y, sh, szh (n_sig, L) float32 -- mixture, step-2
+        output, step-1 output -> DevBuf (n_sig, 3, 2, L) float32 = {sh, y - sh}, {szh, y - szh}, {y, y - sh}, each difference formed in
+        float64 and rounded to float32 once; exact zeros outside [start, stop[i]), where nothing is read.  stop: None (L), a scalar or an
+        (n_sig,) array.  out: optional caller-owned device array of n_sig * 6 * L float32 to write into."""
+        shp = tuple(int(v) for v in y.shape)
+        if len(shp) != 2 or tuple(int(v) for v in sh.shape) != shp or tuple(int(v) for v in szh.shape) != shp:
+            raise ValueError(f'y, sh and szh must all be (n_sig, L): {shp}, {tuple(sh.shape)} and {tuple(szh.shape)}')
+        n_sig, L = shp
+        if min(n_sig, L) < 1:
+            raise ValueError(f'empty batch: {shp}')
+        if stop is not None and not np.ndim(stop):
+            stop = np.full((n_sig,), int(stop), dtype=np.int64)
+        stop, dstop = self._span_stops(stop, n_sig, L, start)
+        if dstop is None and not 0 <= int(start) <= L:
+            raise ValueError(f'need 0 <= start <= L = {L}: start {start}')
+        py, ky = self.to_device(y, np.float32)
+        ps, ks = self.to_device(sh, np.float32)
+        pz, kz = self.to_device(szh, np.float32)
+        if out is None:
+            out = self.empty((n_sig, 3, 2, L), np.float32)
+        else:
+            assert int(np.prod(tuple(out.shape))) == n_sig * 6 * L and not isinstance(out, np.ndarray)
+        po, ko = self.to_device(out, np.float32)
+        self._chk(self.lib.disco_bss_estimates(self.ctx, py, ps, pz, n_sig, L, int(start), None if dstop is None else dstop[0], po, self.stream))
+        return out
 
     STOI_WORKSPACE_BUDGET = 1 << 30     # bytes of workspace one disco_stoi call of Engine.stoi may take
 

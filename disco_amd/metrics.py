@@ -17,10 +17,11 @@ clipping / importance-weight arithmetic of the reference is applied to those.
     third_octave_filterbank   sigproc_utils.py:90-116
 
 `start` / `stop` select the scored span; the reference scores [fs : min_len] (tango.py:541-593), i.e. start = 16000.
-Batches with per-room lengths (Engine.set_lengths): the enhanced signals are exact zeros beyond each room's clip, so the metrics
-that score non-zero samples or inner products (snr, delta_snr, sd, si_sdr, si_bss) need nothing.  fw_snr / fw_sd do NOT handle a
-mixed batch: the band filters ring past the end of a clip, so their non-zero-sample rule would score that tail; they need a
-`start` / `stop` per signal -- call them per group of rooms of one length.
+Batches with per-room lengths (Engine.set_lengths): every metric takes a stop per signal.  `stop` is None (the whole last axis), a
+scalar, or an array shaped like (or broadcastable to) the leading axes -- for bss_eval_sources the leading axes before `nsrc`.  Signal
+i is then scored over [start, stop[i]) exactly as if it had been sliced and scored alone: its band filters stop at its own end, so
+the ringing past a clip is never scored, and nothing at or beyond stop[i] is read -- the padding may hold anything, NaN included.
+speech_enhancement.results_io.batch_results scores a whole batch of rooms this way in one call.
 Band edges: the reference takes them from python-acoustics' OctaveBand (third-party, absent); they are restated from
 IEC 61260-1 (base-10 octave ratio, exact mid-band frequencies) -- the one unpinned piece, see oracle/metrics_oracle.py.
 """
@@ -60,9 +61,19 @@ def _var_nz(cnt, s1, s2):
     return s2 / cnt - mean * mean                                # np.var (ddof 0) of the non-zero samples
 
 
+def _span_stops(stop, lead):
+    """`stop` of a metric -> None / a scalar unchanged, or one stop per flattened signal: an array broadcast over the leading axes."""
+    if stop is None or not np.ndim(stop):
+        return stop
+    try:
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(stop), tuple(lead))).reshape(-1)
+    except ValueError:
+        raise ValueError(f'stop of shape {np.shape(stop)} does not broadcast to the leading axes {tuple(lead)}') from None
+
+
 def _levels(x, start, stop):
     x2, lead = _flat(x)
-    st = _engine().pair_stats(x2, x2, start, stop).numpy()
+    st = _engine().pair_stats(x2, x2, start, _span_stops(stop, lead)).numpy()
     return _var_nz(st[:, 0], st[:, 1], st[:, 2]).reshape(lead)
 
 
@@ -88,7 +99,7 @@ def si_sdr(reference, estimation, start=0, stop=None):
     """metrics.py:342-391 (batched over the leading axes)."""
     r2, lead = _flat(reference)
     e2, _ = _flat(estimation)
-    st = _engine().pair_stats(r2, e2, start, stop).numpy()
+    st = _engine().pair_stats(r2, e2, start, _span_stops(stop, lead)).numpy()
     e_ref, e_est, dot = st[:, 2], st[:, 5], st[:, 6]
     proj = dot * dot / e_ref                                       # |alpha ref|^2
     return (10 * np.log10(proj / (e_est - proj))).reshape(lead)
@@ -102,6 +113,7 @@ def si_bss(estimated_signal, targets, j, scaling=True, start=0, stop=None):
     tg = [_flat(t)[0] for t in targets]
     n_src = len(tg)
     eng = _engine()
+    stop = _span_stops(stop, lead)
     dot = lambda a, b: eng.pair_stats(a, b, start, stop).numpy()[:, 6]
     Rss = np.empty((e2.shape[0], n_src, n_src))
     for p in range(n_src):
@@ -145,6 +157,8 @@ def _raise_on_zero_reference(refs, status, start=0, stop=None, lead=None):
         return
     n_set, nsrc, L = (int(v) for v in refs.shape)
     r2 = refs.reshape(n_set * nsrc, L)
+    if stop is not None and np.ndim(stop):                                    # one stop per set: every source of the set shares it
+        stop = np.repeat(np.asarray(stop).reshape(n_set), nsrc)
     e_ref = _engine().pair_stats(r2, r2, start, stop).numpy()[:, 2]
     zero = np.flatnonzero(e_ref == 0)
     if zero.size:
@@ -164,8 +178,8 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
     with the differences clamped at 0 from below and +inf for a zero denominator.  compute_permutation=True scores every (estimate,
     source) pair and returns, per source j, the figures of estimate perm[j] for the permutation with the best mean SIR; False (what
     tango.py passes) scores estimate j against source j and returns perm = arange(nsrc).
-    `start` / `stop` select the scored span.  A batch of different clip lengths needs nothing: samples past a room's clip are exact
-    zeros in references and estimates alike and add nothing to any sum.
+    `start` / `stop` select the scored span; `stop` may be an array shaped like the leading axes (one stop per reference set), so that a
+    batch of different clip lengths scores every set as if it ran alone, whatever the samples past its clip hold.
     An all-zero reference raises ValueError naming the signal.  Where the references of a set are linearly dependent, or their Gram
     matrix is singular to working precision, that set's figures are NaN (mir_eval falls back to a least-squares solve there)."""
     refs, ests = reference_sources, estimated_sources
@@ -180,6 +194,7 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
     n_set = int(np.prod(lead, dtype=np.int64))
     eng = _engine()
     r3 = refs.reshape(n_set, nsrc, L)
+    stop = _span_stops(stop, lead)
     en, status = eng.bss_eval(r3, ests.reshape(n_set, 1, nsrc, L), start, stop, flen, all_pairs=bool(compute_permutation))
     _raise_on_zero_reference(r3, status, start, stop, lead)
     sdr, sir, sar = _figures(en[:, 0])                                    # (n_set, nsrc[, nsrc])
@@ -255,7 +270,7 @@ def _band_levels(x, b, a, start, stop, gate=None):
         if isinstance(gate, np.ndarray) or not hasattr(gate, 'data_ptr'):
             gate = np.broadcast_to(np.asarray(gate, dtype=np.float32), lead + (x2.shape[-1],))       # one VAD for the whole batch is fine
         g2, _ = _flat(gate)
-    st = _engine().band_stats(x2, b, a, start, stop, gate=g2).numpy()
+    st = _engine().band_stats(x2, b, a, start, _span_stops(stop, lead), gate=g2).numpy()
     return _var_nz(st[..., 0], st[..., 1], st[..., 2]).reshape(lead + (b.shape[0],))
 
 
@@ -271,6 +286,9 @@ def _band_levels2(x, y, b, a, start, stop):
     else:
         import torch
         both = torch.cat([x2, y2], 0)
+    stop = _span_stops(stop, lead)
+    if stop is not None and np.ndim(stop):
+        stop = np.concatenate([stop, stop])
     lv = _band_levels(both, b, a, start, stop)
     n = x2.shape[0]
     return lv[:n].reshape(lead + (b.shape[0],)), lv[n:].reshape(lead + (b.shape[0],))
@@ -286,12 +304,18 @@ def fw_snr(s, n, fs, vad_tar=None, vad_noi=None, clipping=1, db=True, start=0, s
         ls, ln = _band_levels2(s, n, b, a, start, stop)
     else:
         ls, ln = _band_levels(s, b, a, start, stop, gate=vad_tar), _band_levels(n, b, a, start, stop, gate=vad_noi)
-    v = lin2db(ls) - lin2db(ln)
-    if clipping:
-        v = np.minimum(np.maximum(-15, v), 25)
-    fq = I / np.sum(I) * v
-    mean = np.sum(fq, axis=-1)
+    fq, mean = _weighted_band_db(ls, ln, I, -15 if clipping else None)
     return (fq, mean, F) if db else (10 ** (fq / 10), 10 ** (mean / 10), F)
+
+
+def _weighted_band_db(num, den, I, floor):
+    """Band levels (..., n_bands) -> (importance-weighted level ratio per band in dB, its sum over the bands): the arithmetic fw_snr
+    (floor -15) and fw_sd (floor 0) share, metrics.py:113-127, 262-278; floor None: no clipping."""
+    v = lin2db(num) - lin2db(den)
+    if floor is not None:
+        v = np.minimum(np.maximum(floor, v), 25)
+    fq = I / np.sum(I) * v
+    return fq, np.sum(fq, axis=-1)
 
 
 def fw_sd(s_out, s_in, fs, clipping=1, db=True, start=0, stop=None):
@@ -299,9 +323,5 @@ def fw_sd(s_out, s_in, fs, clipping=1, db=True, start=0, stop=None):
     F, I = band_importance(fs)
     b, a = third_octave_filterbank(F, fs, order=4)
     li, lo = _band_levels2(s_in, s_out, b, a, start, stop)
-    v = lin2db(li) - lin2db(lo)
-    if clipping:
-        v = np.minimum(np.maximum(0, v), 25)
-    fq = I / np.sum(I) * v
-    mean = np.sum(fq, axis=-1)
+    fq, mean = _weighted_band_db(li, lo, I, 0 if clipping else None)
     return (fq, mean, F) if db else (10 ** (fq / 10), 10 ** (mean / 10), F)

@@ -167,6 +167,184 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
     return res, resz
 
 
+# ---- a whole batch of rooms in one call -----------------------------------------------------------------------------------------
+def _is_host(a):
+    return isinstance(a, np.ndarray) or not hasattr(a, 'data_ptr')
+
+
+def _batch_array(a, lead, name):
+    """NumPy -> contiguous float32; a device-resident torch tensor stays where it is.  Leading axes checked."""
+    if _is_host(a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    elif not a.is_contiguous():
+        raise ValueError(f'{name}: device tensors must be contiguous')
+    if tuple(int(v) for v in a.shape[:-1]) != tuple(lead):
+        raise ValueError(f'{name}: expected leading axes {tuple(lead)}, got shape {tuple(a.shape)}')
+    return a
+
+
+def _xp(arrays):
+    """numpy, or torch when every array is a device tensor (the stacking below then happens on the device)."""
+    host = [_is_host(a) for a in arrays]
+    if all(host):
+        return np, True
+    if any(host):
+        raise TypeError('batch_results: pass every signal as a NumPy array or every signal as a device-resident torch tensor')
+    import torch
+    return torch, False
+
+
+def _trim(a, L):
+    return a if int(a.shape[-1]) == L else a[..., :L]
+
+
+def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
+                  bss_flen=512, stoi=False, lengths=None):
+    """`room_results` for a whole batch of rooms, clips of different lengths included, in a handful of launches instead of one pass of
+    Python per room: signals (R, K, L), dry sources (R, L), rnd_snrs (R, ...), as NumPy arrays (copied to the device) or -- all of them --
+    device-resident torch tensors (read in place; no signal comes to the host).  lengths (R,): room r is scored over [fs, lengths[r]),
+    the reference's [fs : min_len]; None: the smallest last axis among the signals, for every room, as `room_results` takes it.
+    Samples at and beyond lengths[r] are never read and may hold anything, NaN included.
+    Returns (res, resz) with the keys of `room_results`, every value (R, K) (`snr_in_raw` is rnd_snrs as given); row r holds what
+    `room_results` returns for room r alone on signals cut to lengths[r] (`results_of_room` takes it out).
+    The band levels of a dry source are computed once per room.  The BSS part walks whole rooms in chunks whose workspace stays under
+    Engine.BSS_WORKSPACE_BUDGET: a chunk's estimate sets are formed on the device (Engine.bss_estimates, 24 L bytes per node) and scored
+    twice, against (s_in, n_in) per node and against the room's dry pair with 3 K estimate sets.  An all-zero reference raises
+    ValueError naming the room and the node.  STOI: one Engine.stoi call for all 6 R K pairs, with a stop per pair."""
+    from .. import metrics as dm
+    R, K = (int(v) for v in np.shape(s_in)[:2])
+    bss = y_in is not None and sh_t is not None and szh_t is not None
+    dry = s_dry is not None
+    names = ('s_in', 'n_in', 'sf_t', 'nf_t', 'szf_t', 'nzf_t') + (('y_in', 'sh_t', 'szh_t') if bss else ())
+    given = (s_in, n_in, sf_t, nf_t, szf_t, nzf_t) + ((y_in, sh_t, szh_t) if bss else ())
+    sig = {nm: _batch_array(a, (R, K), nm) for nm, a in zip(names, given)}
+    if dry:
+        sig['s_dry'], sig['n_dry'] = _batch_array(s_dry, (R,), 's_dry'), _batch_array(n_dry, (R,), 'n_dry')
+    xp, host = _xp(list(sig.values()))
+    Lmin = min(int(a.shape[-1]) for a in sig.values())
+    fs = int(fs)
+    if lengths is None:
+        lens = np.full((R,), Lmin, dtype=np.int64)
+    else:
+        lens = np.asarray(lengths)
+        if lens.shape != (R,) or not np.issubdtype(lens.dtype, np.integer):
+            raise ValueError(f'lengths must hold one integer per room, shape ({R},): got {lens.dtype} {lens.shape}')
+        if np.any(lens < fs) or np.any(lens > Lmin):
+            raise ValueError(f'need fs = {fs} <= lengths <= {Lmin}, the shortest signal: {lens}')
+        lens = lens.astype(np.int64)
+    stop_rk = np.repeat(lens, K)                                                          # one stop per (room, node)
+    eng = dm._engine()
+    F, I = dm.band_importance(fs)
+    fb, fa = dm.third_octave_filterbank(F, fs, order=4)
+
+    def levels(nm):
+        """band levels of every signal of `nm` over its own room's span: (R, K, n_bands), or (R, n_bands) for a dry source"""
+        a = sig[nm]
+        lead = tuple(int(v) for v in a.shape[:-1])
+        st = eng.band_stats(a.reshape(-1, int(a.shape[-1])), fb, fa, fs, stop_rk if len(lead) == 2 else lens).numpy()
+        return dm._var_nz(st[..., 0], st[..., 1], st[..., 2]).reshape(lead + (fb.shape[0],))
+
+    nan = np.full((R, K), np.nan)
+    res = {k: nan.copy() for k in RESULT_KEYS_TANGO}
+    resz = {k: nan.copy() for k in RESULT_KEYS_MWF}
+    res['snr_in_raw'] = resz['snr_in_raw'] = rnd_snrs
+    lv = {nm: levels(nm) for nm in ('s_in', 'n_in', 'sf_t', 'nf_t', 'szf_t', 'nzf_t')}
+    fw_snr = lambda num, den: dm._weighted_band_db(num, den, I, -15)[1]
+    fw_sd = lambda out, ref: dm._weighted_band_db(ref, out, I, 0)[1]
+    res['snr_in_cnv'] = resz['snr_in_cnv'] = fw_snr(lv['s_in'], lv['n_in'])              # tango.py:581
+    res['snr_out'] = fw_snr(lv['sf_t'], lv['nf_t'])                                       # :580
+    resz['snr_out'] = fw_snr(lv['szf_t'], lv['nzf_t'])                                    # :584
+    res['fw_sd_cnv'] = fw_sd(lv['sf_t'], lv['s_in'])                                      # :590
+    resz['fw_sd_cnv'] = fw_sd(lv['szf_t'], lv['s_in'])                                    # :592
+    if dry:
+        lsd, lnd = levels('s_dry'), levels('n_dry')                                       # (R, n_bands): once per room
+        res['snr_in_dry'] = resz['snr_in_dry'] = np.repeat(fw_snr(lsd, lnd)[:, None], K, axis=1)      # :582, 586
+        res['fw_sd_dry'] = fw_sd(lv['sf_t'], lsd[:, None, :])                             # :591
+        resz['fw_sd_dry'] = fw_sd(lv['szf_t'], lsd[:, None, :])                           # :593
+    if bss:
+        Lb = min(int(sig[nm].shape[-1]) for nm in ('y_in', 'sh_t', 'szh_t'))
+        y, sh, szh = (_trim(sig[nm], Lb) for nm in ('y_in', 'sh_t', 'szh_t'))
+        Lr = min(Lb, int(sig['s_in'].shape[-1]), int(sig['n_in'].shape[-1]))
+        if dry:
+            Lr = min(Lr, int(sig['s_dry'].shape[-1]), int(sig['n_dry'].shape[-1]))
+        flen = int(bss_flen)
+        per_set = int(eng.lib.disco_bss_workspace_bytes(eng.ctx, 1, 2, flen, Lr))
+        rooms = R if per_set == 0 else max(1, min(R, eng.BSS_WORKSPACE_BUDGET // (per_set * K)))     # per_set 0: bss_eval names the limit
+        cont = (lambda a: np.ascontiguousarray(a)) if host else (lambda a: a.contiguous())
+
+        def figures(refs, est, stops, r0, per_node):
+            """refs (n_set, 2, L), est (n_set, n_est, 2, L) -> sdr, sir, sar of source 0, each (n_set, n_est)"""
+            en, status = eng.bss_eval(refs, est, fs, stops, flen)
+            if np.any(status != 0):
+                n_set = int(refs.shape[0])
+                r2 = refs.reshape(2 * n_set, Lr)
+                e_ref = eng.pair_stats(r2, r2, fs, np.repeat(stops, 2)).numpy()[:, 2]
+                zero = np.flatnonzero(e_ref == 0)
+                if zero.size:
+                    i, j = int(zero[0]) // 2, int(zero[0]) % 2
+                    where = f'room {r0 + i // K}, node {i % K}' if per_node else f'room {r0 + i}, every node (dry sources)'
+                    raise ValueError(f'{where}: reference source {j} is all zero over the scored span')
+            return tuple(v[..., 0] for v in dm._figures(en))
+
+        out = {k: np.empty((R, K, 3)) for k in ('sdr', 'sir', 'sar', 'sdr_dry', 'sir_dry', 'sar_dry')}
+        for r0 in range(0, R, rooms):
+            r1 = min(R, r0 + rooms)
+            n = r1 - r0
+            # (n K, 3, 2, Lr): ests (:547), ests_z (:548), ests_i (:549) of every node of the chunk's rooms
+            ests = eng.bss_estimates(*(cont(_trim(a[r0:r1], Lr)).reshape(n * K, Lr) for a in (y, sh, szh)), start=fs, stop=stop_rk[r0 * K:r1 * K])
+            refs = xp.stack([_trim(sig['s_in'][r0:r1], Lr), _trim(sig['n_in'][r0:r1], Lr)], 2).reshape(n * K, 2, Lr)
+            for key, v in zip(('sdr', 'sir', 'sar'), figures(refs, ests, stop_rk[r0 * K:r1 * K], r0, True)):      # :562-567
+                out[key][r0:r1] = v.reshape(n, K, 3)
+            if dry:                                                                       # :552-560: one reference set, 3 K estimate sets
+                refs = xp.stack([_trim(sig['s_dry'][r0:r1], Lr), _trim(sig['n_dry'][r0:r1], Lr)], 1)
+                for key, v in zip(('sdr_dry', 'sir_dry', 'sar_dry'), figures(refs, ests.reshape(n, 3 * K, 2, Lr), lens[r0:r1], r0, False)):
+                    out[key][r0:r1] = v.reshape(n, K, 3)
+            del ests
+        sdr, sir, sar = out['sdr'], out['sir'], out['sar']
+        res['sdr_cnv'], res['sir_cnv'], res['sar_cnv'] = sdr[..., 0], sir[..., 0], sar[..., 0]
+        resz['sdr_cnv'], resz['sir_cnv'], resz['sar_cnv'] = sdr[..., 1], sir[..., 1], sar[..., 1]
+        res['sdr_in_cnv'] = resz['sdr_in_cnv'] = sdr[..., 2]
+        res['sir_in_cnv'] = resz['sir_in_cnv'] = sir[..., 2]
+        if dry:
+            sdr, sir, sar = out['sdr_dry'], out['sir_dry'], out['sar_dry']
+            res['sdr_dry'], res['sir_dry'], res['sar_dry'] = sdr[..., 0], sir[..., 0], sar[..., 0]
+            resz['sdr_dry'], resz['sir_dry'], resz['sar_dry'] = sdr[..., 1], sir[..., 1], sar[..., 1]
+            res['sdr_in_dry'] = resz['sdr_in_dry'] = sdr[..., 2]
+            res['sir_in_dry'] = resz['sir_in_dry'] = sir[..., 2]
+            res['sar_in_dry'] = resz['sar_in_dry'] = sar[..., 2]
+    if stoi and bss:
+        Ls = Lr
+        flat = lambda a: _trim(a, Ls).reshape(R * K, Ls)
+        clean = [flat(sig['s_in'])]
+        if dry:
+            d2 = _trim(sig['s_dry'], Ls)
+            clean.append((np.repeat(d2, K, axis=0) if host else d2.repeat_interleave(K, dim=0)))
+        cat = (lambda parts: np.concatenate(parts, 0)) if host else (lambda parts: xp.cat(parts, 0))
+        proc = [flat(sig[nm]) for nm in ('y_in', 'sh_t', 'szh_t')]                        # in, out, out_z
+        x = cat([c for c in clean for _ in proc])                                         # (6 R K or 3 R K, Ls): [clean][proc][room][node]
+        yy = cat([p for _ in clean for p in proc])
+        d, status = eng.stoi(x, yy, fs, fs, np.tile(stop_rk, len(clean) * 3))             # tango.py:569-574
+        if np.any(status == 2):
+            i = int(np.flatnonzero(status == 2)[0]) % (R * K)
+            raise ValueError(f'room {i // K}, node {i % K}: the scored span is too short for one frame (fewer than 257 samples at 10 kHz)')
+        if np.any(status == 1):
+            import warnings
+            warnings.warn('Not enough STFT frames to compute intermediate intelligibility measure after removing silent frames. '
+                          'Returning 1e-5. Please check you wav files', RuntimeWarning)
+        d = d.reshape(len(clean), 3, R, K)
+        res['delta_stoi_cnv'] = d[0, 1] - d[0, 0]                                         # :575
+        resz['delta_stoi'] = d[0, 2] - d[0, 0]                                            # :577
+        if dry:
+            res['delta_stoi_dry'] = d[1, 1] - d[1, 0]                                     # :576
+            resz['delta_stoi_dry'] = d[1, 2] - d[1, 0]                                    # :578
+    return res, resz
+
+
+def results_of_room(res, resz, r):
+    """Room r of `batch_results`' two dictionaries: the two per-room dictionaries `room_results` returns and `write_result_pickles` takes."""
+    return {k: np.asarray(v)[r] for k, v in res.items()}, {k: np.asarray(v)[r] for k, v in resz.items()}
+
+
 def write_result_pickles(root, i_rir, noise, res, resz):
     """<root>/OIM/results_tango_<i_rir>_<noise>.p and results_mwf_... (tango.py:634-635)."""
     import pickle

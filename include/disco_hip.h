@@ -124,7 +124,8 @@ int  disco_set_z_blocks(disco_ctx* ctx, int nodes_per_block);
  * [R][K][T][F] with T = disco_n_frames, which does not change); room r is processed as if it had been run alone in a context of
  * length = lengths[r], with T_r = 1 + lengths[r] / hop frames:
  *   - samples at and beyond lengths[r] are never read (they may hold anything, NaN included): the transform reflects or zero-pads at
- *     lengths[r];
+ *     lengths[r].  The metrics honour the same promise through a stop per signal: disco_pair_stats_spans, disco_band_stats_spans,
+ *     disco_lag_corr_spans, disco_bss_eval_spans, disco_bss_estimates and disco_stoi read nothing at or beyond a signal's stop;
  *   - frames t >= T_r do not exist: they enter no statistic; spectra, z, yf and the masks the library computes are exact zeros there.
  *     Masks the CALLER passes in must be FINITE in those frames (their values do not matter);
  *   - output samples n < lengths[r] are the inverse transform with the window sum of T_r frames, n >= lengths[r] exact zeros;
@@ -527,6 +528,12 @@ int disco_crnn_expand_rows(disco_ctx* ctx, const float* rows, int64_t n_rows, in
  *   -> snr / delta_snr / sd (np.var of the non-zero samples, metrics.py:9-61) and si_sdr (:342-391). */
 int disco_pair_stats(disco_ctx* ctx, const float* a, const float* b, int64_t n_sig, int64_t len, int start, int stop,
                      double* stats, disco_stream s);
+/* disco_pair_stats_spans: the same with a span per signal -- rooms of different clip lengths in one launch.  stop: device array of
+ * n_sig int32, clamped into [start, len]; NULL = len for every signal (the rule of disco_stoi).  Pair i is scored over
+ * [start, stop[i]) and stats[i][7] = stop[i] - start; no sample at or beyond stop[i] is read (they may hold anything, NaN included).
+ * Row i has the bits of disco_pair_stats on that pair alone with the scalar stop = stop[i]. */
+int disco_pair_stats_spans(disco_ctx* ctx, const float* a, const float* b, int64_t n_sig, int64_t len, int start, const int32_t* stop,
+                           double* stats, disco_stream s);
 
 /* disco_band_stats: y_j = scipy.signal.lfilter(b[j], a[j], x[i][start:stop]) for every band j (zero initial state at
  * `start`), then stats[i][j][3] = { #(y_j != 0), sum y_j, sum y_j^2 } -- the per-band levels of fw_snr / fw_sd
@@ -537,6 +544,12 @@ int disco_band_stats(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len,
  * a filtered sample enters the statistics where gate != 0 (np.var(s_f[vad != 0])) instead of where the sample itself is non-zero:
  * stats[i][j][3] = { #(gate != 0), sum y_j over them, sum y_j^2 over them }.  gate == NULL: disco_band_stats. */
 int disco_band_stats_gated(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, int stop,
+                           const double* b, const double* a, int n_bands, double* stats, disco_stream s);
+/* disco_band_stats_spans: disco_band_stats (gate == NULL) or disco_band_stats_gated with a span per signal.  stop: device array of
+ * n_sig int32, clamped into [start, len]; NULL = len for every signal.  Signal i is filtered and scored over [start, stop[i]): its
+ * recurrence and its statistics end there, so the ringing of the band filters past the end of a clip is never scored, and neither x
+ * nor gate is read at or beyond stop[i].  stats[i] has the bits of the scalar call on that signal alone with stop = stop[i]. */
+int disco_band_stats_spans(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, const int32_t* stop,
                            const double* b, const double* a, int n_bands, double* stats, disco_stream s);
 
 /* ---- BSS-eval SDR / SIR / SAR (what tango.py:541-567 takes from mir_eval.separation.bss_eval_sources) ---------------
@@ -550,6 +563,12 @@ int disco_band_stats_gated(disco_ctx* ctx, const float* x, const float* gate, in
 size_t disco_lag_corr_workspace_bytes(const disco_ctx* ctx, int64_t n_pair, int64_t len, int n_lag);
 int disco_lag_corr(disco_ctx* ctx, const float* a, const float* b, int64_t n_pair, int64_t len, int start, int stop, int lag_lo,
                    int lag_hi, double* out, void* workspace, size_t workspace_bytes, disco_stream s);
+/* disco_lag_corr_spans: the same with a span per pair.  stop: device array of n_pair int32, clamped into [start, len]; NULL = len for
+ * every pair.  Both signals of pair i count as zero outside [start, stop[i]) and are not read there.  The partial sums are laid out for
+ * the longest span (len - start: the same workspace size) and added in the same chunk order, a chunk past a pair's stop adding zeros:
+ * out[i] has the bits of disco_lag_corr on that pair alone with stop = stop[i]. */
+int disco_lag_corr_spans(disco_ctx* ctx, const float* a, const float* b, int64_t n_pair, int64_t len, int start, const int32_t* stop,
+                         int lag_lo, int lag_hi, double* out, void* workspace, size_t workspace_bytes, disco_stream s);
 
 /* disco_bss_eval: refs [n_set][nsrc][len], ests [n_set][n_est][nsrc][len] float (the n_est estimate sets of a reference set
  * share its factorisation), scored over [start, stop) with a flen-tap filter; 1 <= nsrc <= 4, 1 <= flen <= 512
@@ -568,6 +587,23 @@ size_t disco_bss_workspace_bytes(const disco_ctx* ctx, int64_t n_set, int nsrc, 
 int disco_bss_eval(disco_ctx* ctx, const float* refs, const float* ests, int64_t n_set, int nsrc, int n_est, int64_t len, int start,
                    int stop, int flen, int all_pairs, double* out, int32_t* status, void* workspace, size_t workspace_bytes,
                    disco_stream s);
+/* disco_bss_eval_spans: the same with a span per reference set.  stop: device array of n_set int32, clamped into [start, len]; NULL =
+ * len for every set.  The references of set i and all its estimates are scored over [start, stop[i]) and not read outside it; the
+ * set's energies have the bits of disco_bss_eval on that set alone with stop = stop[i].  An empty span (stop[i] <= start) is an all-zero
+ * reference: status[i] != 0 and NaN energies.  Same workspace; the batch-size limit is taken from len - start. */
+int disco_bss_eval_spans(disco_ctx* ctx, const float* refs, const float* ests, int64_t n_set, int nsrc, int n_est, int64_t len, int start,
+                         const int32_t* stop, int flen, int all_pairs, double* out, int32_t* status, void* workspace, size_t workspace_bytes,
+                         disco_stream s);
+
+/* disco_bss_estimates: the three estimate sets tango.py:547-549 scores per node, formed on the device from the mixture y, the step-2
+ * output sh and the step-1 output szh, each [n_sig][len] float:
+ *   ests[n_sig][3][2][len] = { {sh, y - sh}, {szh, y - szh}, {y, y - sh} }
+ * with every difference (float)((double)a - (double)b): formed in float64 and rounded to float32 once.  stop: device array of n_sig
+ * int32, clamped into [start, len]; NULL = len.  Samples outside [start, stop[i]) are written as exact zeros and not read.  This is the
+ * `ests` argument of disco_bss_eval for n_sig reference sets (n_est = 3, nsrc = 2), and, for n_sig = R K, read as [R][3 K][2][len], the one
+ * for R reference sets of 3 K estimate sets each (the `_dry` keys: one dry pair per room). */
+int disco_bss_estimates(disco_ctx* ctx, const float* y, const float* sh, const float* szh, int64_t n_sig, int64_t len, int start,
+                        const int32_t* stop, float* ests, disco_stream s);
 
 /* ---- STOI (what tango.py:569-578 takes from pystoi.stoi) ------------------------------------------------------------
  * Restated from its definition (Taal, Hendriks, Heusdens, Jensen 2011) with pystoi's constants and conventions; not extended
