@@ -112,6 +112,8 @@ PROTOTYPES = {
     'disco_selftest_room': (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     'disco_selftest_stft_cov_packed': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'disco_selftest_step2_cov_packed': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    'disco_selftest_staged_step2': (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
+    'disco_selftest_pending_matrices': (_int, [_vp, _vp, _vp, _vp]),
     'disco_tango_online': (_int, [_vp, _vp, _vp, _vp, _f, _int, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'disco_online_state_bytes': (_sz, [_vp]),
     'disco_online_stream_workspace_bytes': (_sz, [_vp, _int]),

@@ -35,6 +35,19 @@ int cov_finalize(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s)
                        1.0f / (float)ctx->T, ctx->d_lens, ctx->Kl);
     return check_launch(ctx, "k_cov_finalize");
 }
+
+int pending_matrices(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
+    PendingSums ps;
+    if (!partials_pending(ctx, &ps)) return fail(ctx, DISCO_E_ARG, "disco_selftest_pending_matrices: no partial sums are pending");
+    if (!ps.part_loc) return cov_finalize(ctx, Rss, Rnn, s);
+    if (ps.M_loc < 1 || ps.M_loc > ps.P || ps.blocks_loc < 1)
+        return fail(ctx, DISCO_E_ARG, "disco_selftest_pending_matrices: the pending pencil names no kept step-1 blocks");
+    const long long n_gf = (long long)ctx->cfg.rooms * ctx->Kl * ctx->F;
+    hipLaunchKernelGGL(k_cov_finalize_tail, dim3((unsigned)std::min<long long>((n_gf + 127) / 128, 65535)), dim3(128), 0, (hipStream_t)s,
+                       ps.part, ps.part_loc, (c32*)Rss, (c32*)Rnn, n_gf, ctx->F, ps.blocks, ps.blocks_loc, ps.P, ps.M_loc,
+                       1.0f / (float)ctx->T, ctx->d_lens, ctx->Kl);
+    return check_launch(ctx, "k_cov_finalize_tail");
+}
 static CovArgs cov_args(const disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn, float4* part,
                         int chunks, int mask_remote) {
     CovArgs a;
@@ -52,6 +65,7 @@ static CovArgs cov_args(const disco_ctx* ctx, const disco_c32* X, const float* m
     a.k0 = ctx->k0;
     a.zblk = ctx->zblk;
     a.R = ctx->cfg.rooms;
+    a.lens = ctx->d_lens;
     return a;
 }
 
@@ -155,4 +169,11 @@ extern "C" int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float*
     int rc = cov_partials(ctx, X, mask, Zs, Zn, mask_remote, P, s);
     if (rc || !Rss) return rc;
     return cov_finalize(ctx, Rss, Rnn, s);
+}
+
+// test-only (include/disco_hip.h): cov_finalize for whatever is pending, two-block pencils included
+extern "C" int disco_selftest_pending_matrices(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
+    DISCO_ENTER(ctx);
+    if (!Rss || !Rnn) return fail(ctx, DISCO_E_ARG, "disco_selftest_pending_matrices: null argument");
+    return pending_matrices(ctx, Rss, Rnn, s);
 }

@@ -164,16 +164,41 @@ static bool fused_route(const disco_ctx* ctx) {
 
 // exchange + step-2 statistics with z materialised, mask_for_z = 'local': ONE pass over X for every node of a room where the shape and the
 // context's state allow it (k_room_cov), else the filter pass followed by the covariance pass that reads X again and the K - 1 remote z's
+namespace disco_host {
+int staged_step2(disco_ctx* ctx, const disco_c32* X, const float* mask_w, bool same_mask, const disco_c32* w_loc, disco_c32* z, bool store_z,
+                 disco_stream s, int* route_out) {
+    const disco_cfg& c = ctx->cfg;
+    if (same_mask && room_cov_ok(ctx, X, mask_w)) {
+        if (route_out) *route_out = DISCO_STAGED_ROUTE_ROOM;
+        return STAGE(ctx, s, "room_cov2", room_cov_partials(ctx, X, mask_w, w_loc, z, s, store_z));
+    }
+    int rc = STAGE(ctx, s, "apply1", disco_apply(ctx, X, nullptr, w_loc, c.mics, 1, z, s));
+    if (rc) return rc;
+    const disco_c32* zr = c.nodes > 1 ? z : nullptr;
+    rc = STAGE(ctx, s, "cov2", cov_partials(ctx, X, mask_w, zr, zr, 1, c.mics + c.nodes - 1, s, same_mask && c.nodes > 1));
+    if (route_out) {                           // the step-1 block was skipped <=> the pencil is pending as tail blocks + the kept step-1 blocks
+        PendingSums ps;
+        *route_out = !rc && partials_pending(ctx, &ps) && ps.part_loc ? DISCO_STAGED_ROUTE_SPLIT_SKIPLOC : DISCO_STAGED_ROUTE_WHOLE;
+    }
+    return rc;
+}
+}  // namespace disco_host
+
 static void push_staged_step2(disco_ctx* ctx, Steps& st, const disco_c32* X, const float* mask_w, bool same_mask, const disco_c32* w_loc,
                               disco_c32* z, bool store_z) {
-    st.push_back({nullptr, false, [=](disco_stream s) {
-        const disco_cfg& c = ctx->cfg;
-        if (same_mask && room_cov_ok(ctx, X, mask_w)) return STAGE(ctx, s, "room_cov2", room_cov_partials(ctx, X, mask_w, w_loc, z, s, store_z));
-        const int rc = STAGE(ctx, s, "apply1", disco_apply(ctx, X, nullptr, w_loc, c.mics, 1, z, s));
-        if (rc) return rc;
-        const disco_c32* zr = c.nodes > 1 ? z : nullptr;
-        return STAGE(ctx, s, "cov2", cov_partials(ctx, X, mask_w, zr, zr, 1, c.mics + c.nodes - 1, s, same_mask && c.nodes > 1));
-    }});
+    st.push_back({nullptr, false, [=](disco_stream s) { return staged_step2(ctx, X, mask_w, same_mask, w_loc, z, store_z, s); }});
+}
+
+// test-only (include/disco_hip.h): step 1 on the caller's spectra, then the staged step 2 of the whole-path calls with the same mask
+extern "C" int disco_selftest_staged_step2(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z,
+                                           int store_z, int* route_out, disco_stream s) {
+    DISCO_ENTER(ctx);
+    if (!X || !mask || !w_loc || !z) return fail(ctx, DISCO_E_ARG, "disco_selftest_staged_step2: null argument");
+    if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_selftest_staged_step2: node shard active");
+    if (route_out) *route_out = 0;
+    const int rc = cov_partials(ctx, X, mask, nullptr, nullptr, 1, ctx->cfg.mics, s);      // keeps the step-1 record of X / mask
+    if (rc) return rc;
+    return staged_step2(ctx, X, mask, true, w_loc, z, store_z != 0, s, route_out);
 }
 
 // the global filter + iSTFT: wide shapes in one pass, yf stays on chip (and goes out only when the caller asked for it: yf may be NULL)

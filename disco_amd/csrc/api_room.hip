@@ -44,6 +44,7 @@ int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, con
     a.chunks = chunks;
     a.R = c.rooms;
     a.store_z = store_z ? 1 : 0;
+    a.lens = ctx->d_lens;
     {
         constexpr int nb = 32 / 8;             // bins per workgroup (k_room.h RoomGeomS<M, K, 8>)
         a.tiles = (ctx->F + nb - 1) / nb;

@@ -274,6 +274,13 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
 bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask);
 int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, disco_stream s,
                       bool store_z = true);
+// exchange + step-2 statistics with z materialised (api_path.hip): the room pass where the shape and the context's state allow it, else
+// disco_apply + cov_partials.  The one body behind the whole-path calls and disco_selftest_staged_step2.  route_out (may be NULL): which
+// of DISCO_STAGED_ROUTE_* ran
+int staged_step2(disco_ctx* ctx, const disco_c32* X, const float* mask_w, bool same_mask, const disco_c32* w_loc, disco_c32* z, bool store_z,
+                 disco_stream s, int* route_out = nullptr);
+// cov_finalize for whatever is pending, a pencil left as tail blocks + kept step-1 blocks included (disco_selftest_pending_matrices)
+int pending_matrices(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s);
 // rows of X: the public [T][F][M], or the packed workspace layout [T][F - 1][M] with the Nyquist bin in the DC slot (k_stft.h; 512 points)
 enum class XLayout { Public, Packed };
 // leading M x M block of the step-2 sums: accumulated with the rest, or step 1's -- the caller has checked that the step-1 partial sums of

@@ -56,7 +56,20 @@ struct CovArgs {
     // layout of Zs / Zn: planes [K / zblk][R][zblk] (zblk = K: the plain [R][K]; see z_plane in common.h)
     int zblk;
     long long R;
+    const int* lens;     // [R] per-room clip lengths in samples (nullptr: none): room r has T_r = 1 + lens[r] / (F - 1) <= T frames
 };
+
+// Frames [t0, t1) of chunk c of unit g: chunk c of the T frames of the arrays, cut at the room's own frame count -- nothing at or beyond
+// frame T_r is read, whatever X, the masks and the z rows hold there.  (A chunk wholly beyond T_r is empty; its block is written as zeros.)
+__device__ __forceinline__ void cov_chunk_frames(const CovArgs& a, long long g, int c, int& t0, int& t1) {
+    t0 = (int)(((long long)a.T * c) / a.chunks);
+    t1 = (int)(((long long)a.T * (c + 1)) / a.chunks);
+    if (a.lens) {
+        const int Tr = min(a.T, 1 + a.lens[g / a.Kl] / (a.F - 1));
+        t0 = min(t0, Tr);
+        t1 = min(t1, Tr);
+    }
+}
 
 template <int M, int KR, bool SAMEZ>
 __device__ __forceinline__ void cov_walk(const CovArgs& a, long long g, int f, int t_begin, int t_end, int t_step,
@@ -117,7 +130,8 @@ __global__ __launch_bounds__(NT) void k_cov(CovArgs a) {
     constexpr int P = M + KR, NP = P * (P + 1) / 2;
     const long long g = blockIdx.x / a.chunks;
     const int c = (int)(blockIdx.x % a.chunks);
-    const int t0 = (int)(((long long)a.T * c) / a.chunks), t1 = (int)(((long long)a.T * (c + 1)) / a.chunks);
+    int t0, t1;
+    cov_chunk_frames(a, g, c, t0, t1);
     const int nbin = a.F - 1;
     const bool nyq = (int)threadIdx.x >= nbin;
     const int lane = threadIdx.x & 63;
@@ -240,7 +254,8 @@ __device__ __forceinline__ void cov_big_wave(const CovArgs& a, int M, int KR, lo
     constexpr int NSLOT = (CB_PMAX * (CB_PMAX + 1) / 2 + CB_S - 1) / CB_S;
     const int P = M + KR, NP = P * (P + 1) / 2;
     const int nbin = a.F - 1, tiles = (nbin + 63) / 64;
-    const int t0 = (int)(((long long)a.T * c) / a.chunks), t1 = (int)(((long long)a.T * (c + 1)) / a.chunks);
+    int t0, t1;
+    cov_chunk_frames(a, g, c, t0, t1);
     c32 acc_s[NSLOT], acc_n[NSLOT];
 #pragma unroll
     for (int s = 0; s < NSLOT; ++s) acc_s[s] = acc_n[s] = make_float2(0.f, 0.f);
@@ -444,7 +459,8 @@ __device__ __forceinline__ void cov_split_wave(const CovArgs& a, long long g, in
     } else {
         const int K = a.K, T = a.T, F = a.F;
         const int nbin = F - 1, tiles = (nbin + NBT - 1) / NBT;
-        const int t0 = (int)(((long long)T * c) / a.chunks), t1 = (int)(((long long)T * (c + 1)) / a.chunks);
+        int t0, t1;
+        cov_chunk_frames(a, g, c, t0, t1);
         const bool nyq = tile == tiles;
         int f = nyq ? nbin : tile * NBT + (lane & (NBT - 1));
         const bool live = nyq || f < nbin;
@@ -526,7 +542,8 @@ __device__ __forceinline__ void cov_loc_f64_wave(const CovArgs& a, long long g, 
     } else {
         const int T = a.T, F = a.F;
         const int nbin = F - 1, tiles = (nbin + 63) / 64;
-        const int t0 = (int)(((long long)T * c) / a.chunks), t1 = (int)(((long long)T * (c + 1)) / a.chunks);
+        int t0, t1;
+        cov_chunk_frames(a, g, c, t0, t1);
         const bool nyq = tile == tiles;                                      // the Nyquist bin: lanes are frames
         int f = nyq ? nbin : tile * 64 + lane;
         const bool live = nyq || f < nbin;
@@ -643,7 +660,8 @@ __device__ __forceinline__ void cov_loc_f64_wave_tile(const CovArgs& a, long lon
     constexpr int MH = M / 2, BPR = 16 / MH, D = DISCO_COV64_AHEAD;
     static_assert(M == 8 && NPAIR > 0 && X0 % 2 == 0 && X1 % 2 == 0 && Y0 % 2 == 0 && Y1 % 2 == 0, "whole granules per role; 256 threads = 256 granules");
     const int T = a.T, F = a.F, nbin = F - 1;
-    const int t0 = (int)(((long long)T * c) / a.chunks), t1 = (int)(((long long)T * (c + 1)) / a.chunks);
+    int t0, t1;
+    cov_chunk_frames(a, g, c, t0, t1);
     const int f = tile * 64 + lane;
     const bool live = f < nbin;
     // loader: granule gi = threadIdx.x of the frame-tile = (bin lb, granule lp); bins past the last one re-read it (their weights are zero)
@@ -910,7 +928,8 @@ __device__ __forceinline__ void cov_split_wave_lds(const CovArgs& a, const long 
     constexpr int S = DISCO_COV_STAGE_FRAMES, P = M + KR, NP = P * (P + 1) / 2;
     constexpr int NX = Role::NX, NY = Role::NY, NPAIR = Role::NPAIR, NPA = NPAIR > 0 ? NPAIR : 1;
     const int T = a.T, F = a.F;
-    const int t0 = (int)(((long long)T * c) / a.chunks), t1 = (int)(((long long)T * (c + 1)) / a.chunks);
+    int t0, t1;
+    cov_chunk_frames(a, g, c, t0, t1);
     const int f0 = tile * 64;
     c32 acc_s[NPA], acc_n[NPA];
 #pragma unroll
@@ -1002,6 +1021,46 @@ static __global__ void k_cov_finalize(const float4* __restrict__ part, c32* __re
                 double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
                 for (int c = 0; c < chunks; ++c) {
                     const float4 p = part[(((g * chunks + c) * F) + f) * (long long)NP + q];
+                    sx += (double)p.x;
+                    sy += (double)p.y;
+                    sz += (double)p.z;
+                    sw += (double)p.w;
+                }
+                const double it = lens ? (double)(1.0f / (float)(1 + lens[g / units_per_room] / (F - 1))) : (double)inv_T;
+                float4 s = make_float4((float)(sx * it), (float)(sy * it), (float)(sz * it), (float)(sw * it));
+                if (i == j) s.y = s.w = 0.f;
+                c32* rs = Rss + gf * P * P;
+                c32* rn = Rnn + gf * P * P;
+                rs[i * P + j] = make_float2(s.x, s.y);
+                rn[i * P + j] = make_float2(s.z, s.w);
+                if (i != j) {
+                    rs[j * P + i] = make_float2(s.x, -s.y);
+                    rn[j * P + i] = make_float2(s.z, -s.w);
+                }
+            }
+    }
+}
+
+// k_cov_finalize for a pencil left as TWO sets of partial blocks (test-only, disco_selftest_pending_matrices): the entries (i, j) with
+// j < M_loc come from the kept step-1 blocks part_loc [n_gf/F][chunks_loc][F][M_loc (M_loc + 1) / 2], every other entry from the tail
+// blocks `part` (which hold nothing in the leading block).  Blocks combined in float64, one rounding, as in the solvers' loaders.
+static __global__ void k_cov_finalize_tail(const float4* __restrict__ part, const float4* __restrict__ part_loc, c32* __restrict__ Rss,
+                                           c32* __restrict__ Rnn, long long n_gf, int F, int chunks, int chunks_loc, int P, int M_loc,
+                                           float inv_T, const int* __restrict__ lens, int units_per_room) {
+    const int NP = P * (P + 1) / 2, NPL = M_loc * (M_loc + 1) / 2;
+    for (long long gf = (long long)blockIdx.x * blockDim.x + threadIdx.x; gf < n_gf; gf += (long long)gridDim.x * blockDim.x) {
+        const long long g = gf / F;
+        const int f = (int)(gf % F);
+        int q = 0;
+        for (int i = 0; i < P; ++i)
+            for (int j = i; j < P; ++j, ++q) {
+                const bool loc = j < M_loc;
+                const int nch = loc ? chunks_loc : chunks, np = loc ? NPL : NP;
+                const float4* src = loc ? part_loc : part;
+                const int at = loc ? i * M_loc - (i * (i - 1)) / 2 + (j - i) : q;
+                double sx = 0.0, sy = 0.0, sz = 0.0, sw = 0.0;
+                for (int c = 0; c < nch; ++c) {
+                    const float4 p = src[(((g * nch + c) * F) + f) * (long long)np + at];
                     sx += (double)p.x;
                     sy += (double)p.y;
                     sz += (double)p.z;

@@ -35,6 +35,7 @@ struct RoomArgs {
     int T, F, chunks, tiles;
     long long R;
     int store_z;         // 0: z is only formed on chip (an iteration whose z nobody reads: the next pass re-compresses with new filters)
+    const int* lens;     // [R] per-room clip lengths in samples (nullptr: none): room r has T_r = 1 + lens[r] / (F - 1) <= T frames
 };
 
 // ---- ONE PERSISTENT workgroup per CU, frames fetched by LDS-DMA, time sub-chunks across its lanes ---------------------------------
@@ -226,8 +227,10 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
     const unsigned mxa = (unsigned)((((tid / NB) % K) * T) * F * 4);
 
     // group u of the item (room, f0) into ring slot `slot_`
-    auto issue = [&](int room, int f0, int u, int slot_) {
-        const int tb = u * SUB, tbc = tb < T ? tb : T - 1, nv1 = T - 1 - tbc;         // sub-chunks beyond nv1 repeat frame T - 1
+    // Tr: the room's own frame count (frames_of below).  Nothing at or beyond frame Tr is fetched -- the surplus lanes repeat frame Tr - 1 --
+    // or weighted (fold), and z is an exact zero there (form_z): what X and the mask hold beyond a room's frames does not matter.
+    auto issue = [&](int room, int f0, int u, int slot_, int Tr) {
+        const int tb = u * SUB, tbc = tb < Tr ? tb : Tr - 1, nv1 = Tr - 1 - tbc;      // sub-chunks beyond nv1 repeat frame Tr - 1
         const int bmax = F - 1 - f0;                                                  // bins beyond bmax repeat bin F - 1
         const c32* gx = a.X + (((long long)room * K * T + tbc) * F + f0) * M;
 #pragma unroll
@@ -259,8 +262,9 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
     };
     // z of group u = w^H x of every (frame, node, bin) of the group from ring slot `slot_`: a lane's own granule and taps, then the
     // MH lanes of the bin; published in zs[zb] and stored
-    auto form_z = [&](int room, int f0, int u, int slot_, int zb, int buf) {
+    auto form_z = [&](int room, int f0, int u, int slot_, int zb, int buf, int Tr) {
         const int tb = u * SUB, tbc = tb < T ? tb : T - 1, nv1 = T - 1 - tbc;
+        const int nlive = Tr - tbc;                                                   // a TARGET sub-chunk < nlive is a frame of the room: beyond, z = 0
         const int bmax = F - 1 - f0;
         char* gz = reinterpret_cast<char*>(a.z + ((long long)room * K * T + tbc) * F + f0);
 #pragma unroll
@@ -282,7 +286,9 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
                     // the node's place: lxa = (lk T F M + 2 lp) 8 with 2 lp < M  =>  (lxa >> log2 M) & ~7 = lk T F 8 (bytes of z), and
                     // lwt / (NB MH) = lk (the z rows of a sub-chunk are padded to K + 1)
                     (&sh.zs[zb][0][0][0])[(lsc * (K + 1) + lwt[r] / (NB * MH)) * NB + lbin] = p;
-                    if (a.store_z) *reinterpret_cast<c32*>(gz + ((lxa[r] >> LOGM) & ~7u) + (unsigned)((min(lbin, bmax) + min(lsc, nv1) * F) * 8)) = p;
+                    if (a.store_z)
+                        *reinterpret_cast<c32*>(gz + ((lxa[r] >> LOGM) & ~7u) + (unsigned)((min(lbin, bmax) + min(lsc, nv1) * F) * 8)) =
+                            min(lsc, nv1) < nlive ? p : make_float2(0.f, 0.f);
                 }
             }
         }
@@ -312,9 +318,9 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
 #pragma unroll
     for (int q = 0; q < NACC; ++q) acc_s[q] = acc_n[q] = make_float2(0.f, 0.f);
 
-    auto fold = [&](int f0, int u, int slot_, int zb) {
+    auto fold = [&](int f0, int u, int slot_, int zb, int Tr) {
         const float mkv = sh.ms[slot_][fim / 64][fim % 64];
-        const bool ok = f0 + bin < F && u * SUB + sc < T;
+        const bool ok = f0 + bin < F && u * SUB + sc < Tr;
         const float m = ok ? mkv : 0.f, mc = ok ? 1.f - mkv : 0.f;
         const float wa = m * m, wb = mc * mc;
         const c32(*zs)[NB] = sh.zs[zb][sc];
@@ -424,12 +430,13 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
         const int xcd = w % 8, s_ = w / 8, per = G / 64;          // s_: the workgroup's place on its XCD, per: blocks of 8 items per XCD and round
         return ((n * per + s_ / 8) * 8 + xcd) * 8 + s_ % 8;
     };
+    auto frames_of = [&](int room) { return a.lens ? min(T, 1 + a.lens[room] / (F - 1)) : T; };
     int nr = 0;                                         // round of the issue position
     int Ii = item_of(0), ji = 0, ni = 0;                // item, iteration inside it, ordinal of the item (its tap buffer is n & 1)
     if (Ii >= n_items) return;
-    int ri = Ii / a.tiles, fi = (Ii % a.tiles) * NB;
-    int rf = ri, ff = fi, jf = 0, nf = 0;
-    int rd = ri, fd = fi, jd = 0;
+    int ri = Ii / a.tiles, fi = (Ii % a.tiles) * NB, Ti = frames_of(ri);
+    int rf = ri, ff = fi, jf = 0, nf = 0, Tf = Ti;
+    int rd = ri, fd = fi, jd = 0, Td = Ti;
     bool vi = true, vf = true;                          // position still inside the workgroup's items
     auto advance_issue = [&]() {
         if (++ji == J) {
@@ -438,6 +445,7 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
             if (vi) {
                 ri = Ii / a.tiles;
                 fi = (Ii % a.tiles) * NB;
+                Ti = frames_of(ri);
                 ji = 0;
                 ++ni;
             }
@@ -445,20 +453,20 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
     };
     // prologue: the first item's taps, the first two iterations' groups
     issue_taps(ri, fi, 0);
-    issue(ri, fi, 0, 0);
-    issue(ri, fi, 1, 1);
+    issue(ri, fi, 0, 0, Ti);
+    issue(ri, fi, 1, 1, Ti);
     advance_issue();
-    rf = ri, ff = fi, jf = ji, nf = ni, vf = vi;        // the form position of the first loop iteration is what is issued second
+    rf = ri, ff = fi, jf = ji, nf = ni, vf = vi, Tf = Ti;   // the form position of the first loop iteration is what is issued second
     if (vi) {
         if (ji == 0) issue_taps(ri, fi, ni & 1);
-        issue(ri, fi, 2 * ji, 2);
-        issue(ri, fi, 2 * ji + 1, 3);
+        issue(ri, fi, 2 * ji, 2, Ti);
+        issue(ri, fi, 2 * ji + 1, 3, Ti);
         advance_issue();
     }
     vm_wait_all();
     __syncthreads();                                    // groups 0 ... 3 and the taps are in place
-    form_z(rd, fd, 0, 0, 0, 0);
-    form_z(rd, fd, 1, 1, 1, 0);
+    form_z(rd, fd, 0, 0, 0, 0, Td);
+    form_z(rd, fd, 1, 1, 1, 0, Td);
     __syncthreads();
     int s0 = 0, zb0 = 0;                                // ring slot / z buffer of the fold position's first group
     int rp = rd, fp = fd;                               // the item whose last groups were folded in the previous iteration (pending)
@@ -468,17 +476,17 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
     while (true) {
         if (vi && !(DISCO_ROOM_EXP & 4)) {
             if (ji == 0) issue_taps(ri, fi, ni & 1);    // (the form position left that buffer's item an iteration ago)
-            issue(ri, fi, 2 * ji, (s0 + 4) % D);
-            issue(ri, fi, 2 * ji + 1, (s0 + 5) % D);
+            issue(ri, fi, 2 * ji, (s0 + 4) % D, Ti);
+            issue(ri, fi, 2 * ji + 1, (s0 + 5) % D, Ti);
         }
         if (pending) finish(rp, fp);
         if (vf && !(DISCO_ROOM_EXP & 2)) {
-            form_z(rf, ff, 2 * jf, (s0 + 2) % D, zb0 ^ 2, nf & 1);
-            form_z(rf, ff, 2 * jf + 1, (s0 + 3) % D, (zb0 ^ 2) + 1, nf & 1);
+            form_z(rf, ff, 2 * jf, (s0 + 2) % D, zb0 ^ 2, nf & 1, Tf);
+            form_z(rf, ff, 2 * jf + 1, (s0 + 3) % D, (zb0 ^ 2) + 1, nf & 1, Tf);
         }
         if (!(DISCO_ROOM_EXP & 1)) {
-            fold(fd, 2 * jd, s0, zb0);
-            fold(fd, 2 * jd + 1, (s0 + 1) % D, zb0 + 1);
+            fold(fd, 2 * jd, s0, zb0, Td);
+            fold(fd, 2 * jd + 1, (s0 + 1) % D, zb0 + 1, Td);
         }
         pending = jd == J - 1;
         rp = rd, fp = fd;
@@ -491,8 +499,8 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
         if (!vf) break;                                 // the fold position was this workgroup's last iteration
         s0 = (s0 + 2) % D;
         zb0 ^= 2;
-        rd = rf, fd = ff, jd = jf;
-        rf = ri, ff = fi, jf = ji, nf = ni, vf = vi;
+        rd = rf, fd = ff, jd = jf, Td = Tf;
+        rf = ri, ff = fi, jf = ji, nf = ni, vf = vi, Tf = Ti;
         if (vi) advance_issue();
     }
     finish(rp, fp);

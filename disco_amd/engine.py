@@ -464,6 +464,32 @@ class Engine:
         self._chk(self.lib.disco_selftest_room(self.ctx, ps, n, hw.ptr, ref.ptr, self.stream))
         return hw, ref
 
+    STAGED_ROUTES = {1: 'room', 2: 'split_skiploc', 3: 'whole'}
+
+    def selftest_staged_step2(self, X, mask, w_loc, store_z=True, z=None):
+        """Step 1 on the caller's X (R,K,T,F,M) / mask (R,K,T,F), then the staged step 2 of the whole-path calls with filters w_loc
+        (R,K,F,M) (include/disco_hip.h) -> (z (R,K,T,F), route name); the pencil stays pending for `gevd_mwf_r1_pending(M+K-1)` and
+        `selftest_pending_matrices`.  z: optional caller-owned device array to write into."""
+        px, kx = self.to_device(X, np.complex64)
+        pm, km = self.to_device(mask, np.float32)
+        pw, kw = self.to_device(w_loc, np.complex64)
+        if z is None:
+            z = self.empty((self.R, self.K, self.T, self.F), np.complex64)
+        pz, kz = self.to_device(z, np.complex64)
+        route = C.c_int(0)
+        self._chk(self.lib.disco_selftest_staged_step2(self.ctx, px, pm, pw, pz, int(bool(store_z)), C.addressof(route), self.stream))
+        return z, self.STAGED_ROUTES[int(route.value)]
+
+    def selftest_pending_matrices(self, P):
+        """Rss, Rnn (R,Kl,F,P,P), NumPy, of the pending pencil, one left as tail blocks + kept step-1 blocks included (include/disco_hip.h).
+        The library writes the pending pencil's own P x P (M or M + K - 1): the device arrays are sized for the larger whatever P says."""
+        assert P in (self.M, self.M + self.K - 1), P
+        n, nmax = self.R * self.Kl * self.F * P * P, self.R * self.Kl * self.F * (self.M + self.K - 1) ** 2
+        Rss, Rnn = self.empty((nmax,), np.complex64), self.empty((nmax,), np.complex64)
+        self._chk(self.lib.disco_selftest_pending_matrices(self.ctx, Rss.ptr, Rnn.ptr, self.stream))
+        shape = (self.R, self.Kl, self.F, P, P)
+        return Rss.numpy()[:n].reshape(shape), Rnn.numpy()[:n].reshape(shape)
+
     def reserve(self, own_workspace=1):
         """Allocate now what the whole-path calls would allocate on first use (0: partial-sum blocks only, 1: + the context's
         own workspace of tango_enhance / _iterated / _online, 2: + tango_reference's).  Afterwards a call is a fixed sequence of

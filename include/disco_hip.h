@@ -678,6 +678,31 @@ int disco_selftest_stft_cov_packed(disco_ctx* ctx, const float* y, const float* 
 int disco_selftest_step2_cov_packed(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc, disco_c32* z_out,
                                     disco_c32* Rss, disco_c32* Rnn, int reuse, disco_stream s);
 
+/* The staged step 2 of the whole-path calls on the CALLER's spectra, and the matrices of whatever pencil is pending (tests; no reference
+ * counterpart).  The persistent room pass (csrc/k_room.h) and the split kernels that skip the step-1 block are otherwise reached only from
+ * time signals through disco_tango_enhance*, and leave a pencil the solver assembles from two sets of partial blocks, which
+ * disco_cov_masked / disco_step2_cov_fused never hand out.
+ *   disco_selftest_staged_step2     step 1 on X [R][K][T][F][M] with mask [R][K][T][F] (what disco_cov_masked(X, mask, P = M, NULL, NULL)
+ *                                   runs: it keeps the step-1 sums of X / mask), then exactly what the whole-path calls run for the
+ *                                   exchange + step-2 statistics with the same mask and the filters w_loc [R][K][F][M]: z [R][K][T][F]
+ *                                   (room pass: written only when store_z != 0) and the step-2 pencil left pending for
+ *                                   disco_gevd_mwf_r1_pending.  *route_out (may be NULL): DISCO_STAGED_ROUTE_ROOM the room pass,
+ *                                   _SPLIT_SKIPLOC disco_apply + the split kernel with the step-1 block skipped, _WHOLE disco_apply + a
+ *                                   kernel that sums the whole triangle.  Options "room_cov", disco_set_tuning and disco_set_lengths
+ *                                   apply as in the whole path (per-room lengths: the statistics and the room pass read nothing beyond a
+ *                                   room's frames; disco_apply does, so off the room pass X must hold zeros there, as the library's own
+ *                                   spectra do).  No node shard.
+ *   disco_selftest_pending_matrices Rss, Rnn [R][Kl][F][P][P] of the pending pencil (it stays pending): the partial blocks combined in
+ *                                   float64, scaled by 1 / T (1 / T_r under per-room lengths) and rounded once, mirrored.  A pencil pending as
+ *                                   tail blocks takes the entries with both indices below M from the kept step-1 blocks, as the solvers'
+ *                                   loaders do; a whole-triangle pencil gives the bits disco_cov_masked hands out. */
+#define DISCO_STAGED_ROUTE_ROOM 1
+#define DISCO_STAGED_ROUTE_SPLIT_SKIPLOC 2
+#define DISCO_STAGED_ROUTE_WHOLE 3
+int disco_selftest_staged_step2(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* w_loc, disco_c32* z, int store_z,
+                                int* route_out, disco_stream s);
+int disco_selftest_pending_matrices(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s);
+
 #define DISCO_PK_SELFTEST_OPS 23
 int disco_selftest_pk(disco_ctx* ctx, const disco_c32* a, const disco_c32* b, const disco_c32* c, int64_t n,
                       disco_c32* out_hw, disco_c32* out_ref, disco_stream s);

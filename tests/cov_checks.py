@@ -22,8 +22,10 @@ tables out of the headers and asserts that `exact_cases` launches every name `ro
                                                 k_stft + k_cov_loc_f64<M>      M = 7, 8 at 1024 points (the staged pair)
     UNREACHABLE (instantiated, never launched): k_cov<7, 0, ..> and k_cov<8, 0, ..> (both hidden behind k_cov_loc_f64: cov_partials
         walks DISCO_FOR_MKR only when its split test fails, and (7, 0), (8, 0) are in DISCO_FOR_SPLIT_M8), k_cov<M, 0, false, ..> (a step-1 call has no Zn).
-    WHOLE PATH ONLY (not reachable from a staged call; run by tests/test_gpu_parity.py::test_room_cov_* / test_wide_* and
-        tests/test_gpu_wide_network.py through disco_tango_enhance): k_cov_split_lds<M, KR, true>, k_room_cov.
+    disco_selftest_staged_step2 (through the test-only entry: step 1 on the caller's X, then the staged step 2 of the whole-path calls;
+    tests/room_checks.py holds these two, and the re-use route, to the exact tier)
+        (M, K) in the room table, "room_cov" = 1  k_room_cov_dma<M, K, 8>        the persistent one-pass room kernel, 6 shapes
+        (M, K - 1) in the split tables, K >= 2    k_cov_split_lds<M, KR, true>   the step-1 block skipped, 24 shapes
 
 THE EXACT TIER.  A covariance is a sum of products.  The scenes here hold spectra whose real and imaginary parts are small integers and
 masks from {0, 1/4, 1/2, 3/4, 1}: m x, m^2, (1 - m)^2 and every product are multiples of 1/16, so every partial sum -- in any order,
@@ -48,9 +50,11 @@ so that more than nine pencils in ten are held to that floor (asserted).
 Which solver's loader reads which family's blocks is the table PENDING (every one of the four is reached).  This bar is recomputed on
 the inputs of every run, not committed as a table.
 
-THE RE-USE ROUTE (disco_step2_cov_fused_reuse) hands out no matrices and takes its spectra from disco_stft_cov_fused, so nothing of it
-can be exact: `check_reuse` holds its z_out bit-identical to the non-reuse call's and compares its pending solve per pencil on all 28
-shapes, with the float32 restatement of the sums as the reference-side perturbation.  THE FLOAT TIERS (the staged families at 626
+THE RE-USE ROUTE (disco_step2_cov_fused_reuse) hands out no matrices and, after disco_stft_cov_fused, works on transformed spectra that
+cannot be exact: `check_reuse` holds its z_out bit-identical to the non-reuse call's and compares its pending solve per pencil on all 28
+shapes, with the float32 restatement of the sums as the reference-side perturbation.  (tests/room_checks.py `check_reuse_exact` holds the
+same kernel to the exact tier: step 1 established by disco_cov_masked on an exact scene, the matrices read by the test-only
+disco_selftest_pending_matrices.)  THE FLOAT TIERS (the staged families at 626
 frames in one chunk; disco_stft_cov_fused against the complex128 transform) are described above `check_float` and `check_stft_cov`.
 """
 import re
@@ -74,11 +78,12 @@ CB_PMAX, CW_PMAX = 16, 32
 
 UNREACHABLE = tuple(f'k_cov<{m},0,{s},{nt}>' for m in (7, 8) for s in ('true', 'false') for nt in (320, 576)) \
     + tuple(f'k_cov<{m},0,false,{nt}>' for m in range(1, 7) for nt in (320, 576))
-WHOLE_PATH_ONLY = {
-    'k_cov_split_lds<M,KR,true>': 'tests/test_gpu_parity.py::test_room_cov_route_off, tests/test_gpu_wide_network.py (disco_tango_enhance, '
-                                  'staged wide route with the step-1 block re-used)',
-    'k_room_cov': 'tests/test_gpu_parity.py::test_room_cov* (disco_tango_enhance, option "room_cov" = 1)',
-}
+ROOM = ((8, 8), (8, 6), (8, 4), (8, 2), (4, 8), (4, 6))                                # DISCO_FOR_ROOM (dispatch.h): (M, K); SUB = 8 (api_room_s8.hip)
+
+
+def selftest_reachable():
+    """The kernels only disco_selftest_staged_step2 reaches from a staged call (tests/room_checks.py runs them)."""
+    return {f'k_room_cov_dma<{M},{K},8>' for M, K in ROOM} | {f'k_cov_split_lds<{M},{KR},true>' for M, KR in SPLIT if KR > 0}
 
 
 def _b(x):
@@ -119,9 +124,10 @@ def route(M, K, n_fft, step2, same_z=True, mask_remote=True, call='cov_masked'):
     return (f'k_cov_big<{_b(same)}>',)
 
 
-def reachable():
-    """Every kernel name `route` can return for a staged covariance call (the exact tier's and the re-use route's)."""
-    names = set()
+def reachable(selftest=True):
+    """Every kernel name `route` can return for a staged covariance call (the exact tier's and the re-use route's) and, with `selftest`,
+    the ones the test-only entry adds."""
+    names = selftest_reachable() if selftest else set()
     for n_fft in (512, 1024):
         for M in range(1, 9):
             for K in range(1, 34):

@@ -9,6 +9,7 @@ import re
 import numpy as np
 
 import cov_checks as cc
+import room_checks as rc
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, 'disco_amd', 'csrc')
@@ -69,10 +70,17 @@ def test_route_restates_the_dispatch_order():
 
 def test_case_list_launches_every_reachable_instantiation():
     reach = cc.reachable()
-    launched = cc.launched_by(cc.exact_cases()) | {f'k_step2_cov_fused<{M},{K},true>' for M, K in cc.reuse_shapes()}
+    launched = cc.launched_by(cc.exact_cases()) | {f'k_step2_cov_fused<{M},{K},true>' for M, K in cc.reuse_shapes()} \
+        | rc.launched_by(rc.staged_cases())
     assert launched == reach, (sorted(reach - launched), sorted(launched - reach))
-    # 2 FFT sizes x (6 step-1 + 28 step-2 x 2) k_cov, 2 k_cov_loc_f64, 24 k_cov_split_lds, 2 + 2, 36 + 28 fused
-    assert len(reach) == 2 * (6 + 56) + 2 + 24 + 4 + 36 + 28
+    # 2 FFT sizes x (6 step-1 + 28 step-2 x 2) k_cov, 2 k_cov_loc_f64, 24 k_cov_split_lds, 2 + 2, 36 + 28 fused; through the test-only entry
+    # the 24 k_cov_split_lds<.., true> and the 6 shapes of the room pass
+    assert len(reach) == 2 * (6 + 56) + 2 + 24 + 4 + 36 + 28 + 24 + 6
+    assert cc.reachable(selftest=False) | cc.selftest_reachable() == reach and not cc.reachable(selftest=False) & cc.selftest_reachable()
+    # the staged calls alone launch what they launched before, and the new cases launch every name the test-only entry adds -- by themselves
+    assert cc.launched_by(cc.exact_cases()) | {f'k_step2_cov_fused<{M},{K},true>' for M, K in cc.reuse_shapes()} == cc.reachable(selftest=False)
+    assert cc.selftest_reachable() <= rc.launched_by(rc.staged_cases())
+    assert {(M, K) for M, K, _t in rc.reuse_cases()} == set(cc.reuse_shapes())
     # what the (M, KR) table instantiates and no staged call reaches is listed as such: k_cov<7, 0>, k_cov<8, 0> sit behind
     # k_cov_loc_f64 ((7, 0) and (8, 0) are split shapes and the split test comes first), and a step-1 call never has distinct Zn
     inst = {f'k_cov<{M},{KR},{s},{nt}>' for M, KR in cc.MKR for s in ('true', 'false') for nt in (320, 576)}
@@ -103,7 +111,7 @@ def test_committed_kernel_trace_holds_every_reachable_name():
     traced = {cc.kernel_key(l) for l in lines}
     stft = {n for M in range(1, 9) for n_fft in (512, 1024) for n in cc.route(M, 1, n_fft, False, call='stft_cov') if n != 'k_stft'}
     assert len(stft) == 14 + 2                   # k_stft_cov<512, 1 .. 8>, <1024, 1 .. 6>; the staged pair ends in k_cov_loc_f64<7>, <8>
-    missing = sorted((cc.reachable() | stft) - traced)
+    missing = sorted((cc.reachable(selftest=False) | stft) - traced)     # (the trace is of tests/test_gpu_cov_routes.py: the staged calls)
     assert not missing, missing
     assert not traced & set(cc.UNREACHABLE), sorted(traced & set(cc.UNREACHABLE))
 
@@ -230,3 +238,87 @@ def test_committed_stft_distances_match_recomputation():
     assert {c['pad'] for c in cases} == {'reflect', 'constant'} and {c['runw'] for c in cases} >= {8, 40, 79, 80, 400}
     assert {c['T'] for c in cases} >= {2, 3} and any(c['runw'] > c['T'] for c in cases) and sum(c['frames'] is not None for c in cases) >= 3
     assert any(c['runw'] and c['T'] % (4 * c['runw']) and c['T'] % (4 * c['runw']) <= c['runw'] for c in cases)      # empty waves at the end
+
+
+def test_room_tables_and_staged_step2_restate_the_host_code():
+    """The tables and the route rule of tests/room_checks.py against dispatch.h / api_room.hip / api_path.hip / api_cov.hip; the source
+    lines are pinned verbatim on purpose (a drift alarm, as in test_route_restates_the_dispatch_order)."""
+    tables = _read(CSRC, 'dispatch.h')
+    assert _table(tables, 'DISCO_FOR_ROOM') == cc.ROOM == rc.ROOM
+    assert 'k_room_cov_dma<M_, K_, 8>' in _read(CSRC, 'api_room_s8.hip') and rc.ROOM_SUB == 8
+    assert int(re.search(r'#define DISCO_ROOM_DEPTH (\d+)', _read(CSRC, 'k_room.h')).group(1)) == rc.ROOM_DEPTH
+    assert len(rc.SPLIT_SHAPES) == 24 and all(8 < M + K - 1 <= cc.CB_PMAX for M, K in rc.SPLIT_SHAPES)
+    path = _read(CSRC, 'api_path.hip')
+    marks = ['int staged_step2(disco_ctx* ctx,', 'if (same_mask && room_cov_ok(ctx, X, mask_w)) {', 'room_cov_partials(ctx, X, mask_w, w_loc, z, s, store_z)',
+             'disco_apply(ctx, X, nullptr, w_loc, c.mics, 1, z, s)', 'cov_partials(ctx, X, mask_w, zr, zr, 1, c.mics + c.nodes - 1, s, same_mask && c.nodes > 1)',
+             'static void push_staged_step2(', 'return staged_step2(ctx, X, mask_w, same_mask, w_loc, z, store_z, s);',
+             'extern "C" int disco_selftest_staged_step2(', 'cov_partials(ctx, X, mask, nullptr, nullptr, 1, ctx->cfg.mics, s);',
+             'return staged_step2(ctx, X, mask, true, w_loc, z, store_z != 0, s, route_out);']
+    at = [path.index(m) for m in marks]
+    assert at == sorted(at)
+    assert path.count('room_cov_partials(') == 1 and path.count('staged_step2(ctx, X, mask') == 2      # ONE body behind the whole path and the entry
+    room = _read(CSRC, 'api_room.hip')
+    assert 'if (!want || !shape || M + K - 1 <= 8 || sharded(ctx) || !X || !mask) return false;' in room
+    assert 'skiploc = skiploc && split && KR > 0 && step1_held(ctx, X, mask);' in _read(CSRC, 'api_cov.hip')
+    hdr = _read(REPO, 'include', 'disco_hip.h')
+    from disco_amd.engine import Engine
+    for name, code in (('ROOM', 'room'), ('SPLIT_SKIPLOC', 'split_skiploc'), ('WHOLE', 'whole')):
+        n = int(re.search(r'#define DISCO_STAGED_ROUTE_' + name + r' (\d+)', hdr).group(1))
+        assert Engine.STAGED_ROUTES[n] == code
+    # spot values
+    assert rc.expected_route(8, 8, 1) == 'room' and rc.expected_route(8, 8, 0) == 'split_skiploc' and rc.expected_route(4, 4, 1) == 'whole'
+    assert rc.expected_route(2, 8, 1) == 'split_skiploc' and rc.expected_route(3, 8, 0) == 'whole' and rc.expected_route(2, 16, 0) == 'whole'
+    assert rc.kernel_of(4, 6, 512, 1) == 'k_room_cov_dma<4,6,8>' and rc.kernel_of(4, 6, 512, 0) == 'k_cov_split_lds<4,5,true>'
+
+
+def test_room_cases_hold_what_the_checks_claim():
+    """The shapes and edges of the staged-step-2 tier, counted on the case list itself."""
+    cases = rc.staged_cases()
+    room = [c for c in cases if rc.expected_route(c['M'], c['K'], c['room_cov']) == 'room']
+    split = [c for c in cases if rc.expected_route(c['M'], c['K'], c['room_cov']) == 'split_skiploc']
+    assert len(room) + len(split) == len(cases)
+    assert {(c['M'], c['K'], c['n_fft']) for c in room} == {(M, K, n) for M, K in rc.ROOM for n in (512, 1024)}
+    assert {(c['M'], c['K']) for c in split} >= set(rc.SPLIT_SHAPES) and any(c['n_fft'] == 1024 for c in split)
+    for M, K in ((8, 2), (4, 6)):                                          # every frame count around the ring on these two
+        assert {c['T'] for c in room if (c['M'], c['K'], c['n_fft'], c['R']) == (M, K, 512, 1)} >= set(rc.RING_T)
+    assert set(rc.RING_T) == {1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 47, 48, 49}
+    for M, K in rc.ROOM:
+        assert {c['T'] for c in room if (c['M'], c['K']) == (M, K)} >= set(rc.RING_T_SUBSET)
+    # item walking: 65 tiles per room at 512 points over min(items, CUs) workgroups rounded down to a multiple of 64
+    def walks(R, tiles=65, cus=256):
+        items = R * tiles
+        nwg = min(items, cus)
+        nwg = max(64, nwg // 64 * 64) if items >= 64 else nwg
+        return -(-items // nwg)
+    assert [walks(R) for R in (1, 2, 8)] == [2, 2, 3]
+    assert {c['R'] for c in room if c['n_fft'] == 512 and not c.get('frames')} >= {1, 2, 8}
+    lens = [c for c in room if c.get('frames')]
+    assert any(c['R'] == 8 for c in lens) and all(max(c['frames']) == c['T'] for c in lens)
+    assert any(a == 1 and b == c['T'] or a == c['T'] and b == 1 for c in lens for a, b in zip(c['frames'], c['frames'][1:]))   # one frame next to a full room
+    assert sum(c.get('store_z') is False for c in room) >= 3
+    # the split route: frame counts either side of its chunk boundaries, fewer frames than chunks, lengths
+    geo = {(c['T'], c.get('chunks', 0)) for c in split}
+    assert geo >= set(rc.SPLIT_GEOMETRY) and {(15, 2), (16, 2), (17, 2), (31, 4), (32, 4), (33, 4)} <= geo and any(ch > T for T, ch in geo)
+    assert any(c.get('frames') for c in split)
+    # pending solves (every room >= 4 P frames) on both routes, P = 9 and beyond
+    solved = [c for c in cases if min(c.get('frames') or (c['T'],)) >= 4 * (c['M'] + c['K'] - 1)]
+    assert {c['room_cov'] for c in solved} == {0, 1} and len({c['M'] + c['K'] - 1 for c in solved}) >= 3
+    assert max(c['T'] for c in cases) <= 49
+    assert len({rc.case_id(c) for c in cases}) == len(cases)
+
+
+def test_room_filters_and_scenes_are_exact():
+    """Two or three taps from {+-1, +-i, +-1 +- i}; z = w^H x is an integer and the representability bound holds at the longest and the widest
+    cases (ref_sums asserts it on every case the checks build)."""
+    w = rc.room_filters(3, 2, 8, 33, 8)
+    nz = (w != 0).sum(axis=-1)
+    assert nz.min() >= 1 and nz.max() == 3 and (nz >= 2).mean() > 0.8
+    assert set(np.unique(w[w != 0])) <= set(rc.TAPS) and len(set(np.unique(w[w != 0]))) == 8
+    for M, K, T in ((8, 8, 49), (4, 8, 49), (2, 15, 49), (8, 9, 49)):
+        X, _zs, _zn, mask = cc.scene(5, 1, K, M, T, 17, False)
+        z = rc.exact_z(X, rc.room_filters(7, 1, K, 17, M))
+        assert np.array_equal(z, np.round(z.real) + 1j * np.round(z.imag)) and np.abs(z.real).max() <= 18
+        zc = z.astype(np.complex64)
+        assert np.array_equal(zc.astype(np.complex128), z)
+        Sss, Snn = cc.ref_sums(X, mask, zc, zc, True)
+        assert Sss.shape == (1, K, 17, M + K - 1, M + K - 1)
