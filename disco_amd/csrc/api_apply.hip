@@ -36,7 +36,7 @@ extern "C" int disco_apply(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
     int t_chunks = (int)std::min<long long>(std::max<long long>(1, (DISCO_APPLY_ITEMS + Gg * tiles - 1) / (Gg * tiles)), std::max(1, ctx->T / 8));
     while (G * tiles * t_chunks > 0x7ffffff0LL && t_chunks > 1) t_chunks >>= 1;
     const long long items_m = G * tiles * t_chunks;
-    const dim3 grid_m((unsigned)((items_m + DISCO_APPLY_XCD - 1) / DISCO_APPLY_XCD * DISCO_APPLY_XCD));      // ids are dealt over the XCDs
+    const dim3 grid_m((unsigned)xcd_grid(items_m));      // ids are dealt over the XCDs
     // the three wave-per-tile kernels take the same arguments
     const auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid_m, dim3(64), 0, st, Xc, Zc, wc, (c32*)out, KR, c.nodes, ctx->T, ctx->F, conj_w, tiles, t_chunks, ctx->Kl,

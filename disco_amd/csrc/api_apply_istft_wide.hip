@@ -37,7 +37,7 @@ int apply_istft_wide(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, con
     const int run_len = 2 * pairs - 1;
     const int chunks = (n_seg + WV * run_len - 1) / (WV * run_len);
     const long long items = (long long)c.rooms * ctx->Kl * chunks;
-    const long long nblk = (items + 7) / 8 * 8;
+    const long long nblk = xcd_grid(items);
     if (nblk > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_tango_enhance: batch too large for one launch");
     ApplyIstftWideArgs a;
     a.X = (const c32*)X;

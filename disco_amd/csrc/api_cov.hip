@@ -79,7 +79,7 @@ static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* ma
     const int NP = P * (P + 1) / 2, tiles = (ctx->F - 1 + 63) / 64;
     const int nbg = (cov_wide_blocks(P) + CW_WAVES - 1) / CW_WAVES;
     const long long n_items = G * (tiles + 1) * chunks * nbg;
-    const long long grid = (n_items + DISCO_COV_WIDE_XCD - 1) / DISCO_COV_WIDE_XCD * DISCO_COV_WIDE_XCD;
+    const long long grid = xcd_grid(n_items);
     if (grid > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: batch too large (P > 16: more than 2^31 workgroups)");
     // the block this batch needs, G x chunks x F x NP x 16 B, checked before anything runs
     const size_t need = (size_t)G * chunks * ctx->F * NP * sizeof(float4);

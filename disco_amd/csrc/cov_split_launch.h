@@ -16,7 +16,7 @@ static void launch_cov_split(bool skiploc, unsigned nblk, hipStream_t st, const 
     // staged through LDS once per workgroup (k_cov.h; with remote rows 7.3 ms per C5 launch, the per-wave fetches of k_cov_split: 9.6 ms)
     if constexpr (M % 2 == 0) {
         if (KR > 0) {               // (a run-time test: k_cov_split_lds<8, 0, false> is built and never run)
-            const unsigned nb = DISCO_COV_XCD ? (nblk + DISCO_COV_XCD - 1) / DISCO_COV_XCD * DISCO_COV_XCD : nblk;      // see the kernel's id -> item map
+            const unsigned nb = (unsigned)xcd_grid(nblk);      // see the kernel's id -> item map
             with_bool(skiploc, [&](auto skip) {
                 constexpr bool SKIP = KR > 0 && decltype(skip)::value;
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_split_lds<M, KR, SKIP>), dim3(nb), dim3(64 * cov_split_waves<KR, SKIP>()), 0, st, a);

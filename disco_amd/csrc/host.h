@@ -39,6 +39,11 @@ struct OptionInfo {
 const OptionInfo* option_table();
 }  // namespace disco_host
 
+// workgroups for n logical items dealt over the XCDs by disco::xcd_item (common.h): the next multiple of N_XCD
+namespace disco_host {
+inline long long xcd_grid(long long n) { return (n + disco::N_XCD - 1) / disco::N_XCD * disco::N_XCD; }
+}  // namespace disco_host
+
 // a library-owned device allocation that only ever grows (disco_host::grow); freed by disco_destroy
 struct DevBlock {
     void* p = nullptr;

@@ -48,9 +48,6 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(256) void k_apply(const c32* __r
 // BIN for a run of frames and keeps the bin's filter in registers.  M is a template parameter (the node's own M-vector is
 // one unrolled, vectorised load); the remote count KR is a run-time value walked by a fully unrolled, wave-uniformly
 // predicated loop (at most 15 remote rows).  One wave per workgroup: 64 consecutive bins x frames [t0, t1).
-#ifndef DISCO_APPLY_XCD
-#define DISCO_APPLY_XCD 8             // XCDs the workgroup ids of k_apply_m are dealt over
-#endif
 // KRMAX: the remote rows the loop is unrolled for (15: P <= 16 with M >= 1 ... ; 31: the wide networks, 17 <= P <= 32)
 template <int M, int KRMAX = 15>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64) void k_apply_m(const c32* __restrict__ X, const c32* __restrict__ Z,
@@ -59,12 +56,11 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64) void k_apply_m(const c32* __
                                                  long long R) {
     const int P = M + KR;
     // Which workgroup does what: the Kl nodes of a room read the same K - 1 remote rows of a (tile, frame chunk), so they are made
-    // neighbours on ONE XCD (one L2), as in k_cov_split_lds: the hardware deals consecutive workgroup ids round-robin to the 8
-    // XCDs, hence id b is logical item (b % 8) * (grid / 8) + b / 8 (the grid is padded to a multiple of 8), and logical items run
-    // node-fastest.  (With node-major ids node k's tile t sits on XCD (k + t) % 8: every remote row crossed the fabric K - 1
-    // times -- PMC at C5: 32.1 GB read per launch against 18.5 GB of distinct bytes.)
+    // neighbours on ONE XCD (xcd_item, common.h), as in k_cov_split_lds: logical items run node-fastest.  (With node-major ids node k's
+    // tile t sits on XCD (k + t) % 8: every remote row crossed the fabric K - 1 times -- PMC at C5: 32.1 GB read per launch against
+    // 18.5 GB of distinct bytes.)
     const long long n_items = R * Kl * (long long)tiles * t_chunks;
-    long long item = (long long)(blockIdx.x % DISCO_APPLY_XCD) * (gridDim.x / DISCO_APPLY_XCD) + blockIdx.x / DISCO_APPLY_XCD;
+    long long item = xcd_item();
     if (item >= n_items) return;
     const int kl = (int)(item % Kl);
     item /= Kl;
@@ -131,7 +127,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64) void k_apply_mq(const c32* _
     __shared__ float4 sx[64 * MH];
     const int P = M + KR;
     const long long n_items = R * Kl * (long long)tiles * t_chunks;
-    long long item = (long long)(blockIdx.x % DISCO_APPLY_XCD) * (gridDim.x / DISCO_APPLY_XCD) + blockIdx.x / DISCO_APPLY_XCD;
+    long long item = xcd_item();
     if (item >= n_items) return;
     const int kl = (int)(item % Kl);
     item /= Kl;

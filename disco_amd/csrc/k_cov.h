@@ -354,45 +354,20 @@ __device__ __forceinline__ void cov_split_fetch(c32* u, const c32* __restrict__ 
     for (int c = ZA; c < C1; ++c) u[c - C0] = zp[c - M][tf];
 }
 
-// acc += (wa, wb) x { u_i conj(u_j) } over the role's pairs (TRI: the two upper triangles of X and Y, else the X x Y block)
-#ifndef DISCO_COV_PK
-#define DISCO_COV_PK 2
-#endif
-#if DISCO_COV_PK == 2
-// on the instruction forms of pk.h: u_i conj(u_j) in two packed instructions, one packed fma per statistic (weights broadcast
-// from the pair (wa, wb) by the operand selectors) -- as cov_accumulate_shared
+// acc += (wa, wb) x a conj(b) on the instruction forms of pk.h: the product in two packed instructions, one packed fma per statistic
+// (weights broadcast from the pair (wa, wb) by the operand selectors) -- as cov_accumulate_shared
 __device__ __forceinline__ void cov_pair_acc(const c32 a, const c32 b, const float wa, const float wb, c32& as, c32& an) {
     const c32 p = cmul_aconjb(a, b), w2 = make_float2(wa, wb);
     as = fma_by_half<0>(p, w2, as);
     an = fma_by_half<1>(p, w2, an);
 }
-#elif DISCO_COV_PK && DISCO_PK && defined(__clang__)
-// packed form: (pr, pi) = a conj(b) as v_pk_mul + v_pk_fma, then one v_pk_fma per part on the pair (Rss, Rnn) of sums -- 4
-// instructions per pair of components instead of 8; the sums live as (acc_s.x, acc_n.x), (acc_s.y, acc_n.y)
-__device__ __forceinline__ void cov_pair_acc(const c32 a, const c32 b, const float wa, const float wb, c32& as, c32& an) {
-    const v2f w2 = {wa, wb};
-    const v2f p = __builtin_elementwise_fma(v2f{a.x, a.x}, v2f{b.x, -b.y}, v2f{a.y, a.y} * v2f{b.y, b.x});
-    const v2f re = __builtin_elementwise_fma(w2, v2f{p.x, p.x}, v2f{as.x, an.x});
-    const v2f im = __builtin_elementwise_fma(w2, v2f{p.y, p.y}, v2f{as.y, an.y});
-    as = make_float2(re.x, im.x);
-    an = make_float2(re.y, im.y);
-}
-#else
-__device__ __forceinline__ void cov_pair_acc(const c32 a, const c32 b, const float wa, const float wb, c32& as, c32& an) {
-    const float pr = fmaf(a.x, b.x, a.y * b.y);          // a conj(b)
-    const float pi = fmaf(a.x, -b.y, a.y * b.x);
-    as.x = fmaf(wa, pr, as.x);
-    an.x = fmaf(wb, pr, an.x);
-    as.y = fmaf(wa, pi, as.y);
-    an.y = fmaf(wb, pi, an.y);
-}
-#endif
 __device__ __forceinline__ void cov_diag_acc(const c32 a, const float wa, const float wb, c32& as, c32& an) {
     const float pr = fmaf(a.x, a.x, a.y * a.y);
     as.x = fmaf(wa, pr, as.x);
     an.x = fmaf(wb, pr, an.x);
 }
 
+// acc += (wa, wb) x { u_i conj(u_j) } over the role's pairs (TRI: the two upper triangles of X and Y, else the X x Y block)
 template <class Role, bool TRI, int NX, int NY>
 __device__ __forceinline__ void cov_split_accumulate(const c32* ux, const c32* uy, const float wa, const float wb, c32* acc_s,
                                                      c32* acc_n) {
@@ -833,9 +808,6 @@ __device__ __forceinline__ void cov_split_roles(const int role, Fn&& fn) {
 #ifndef DISCO_COV_STAGE_FRAMES
 #define DISCO_COV_STAGE_FRAMES 2
 #endif
-#ifndef DISCO_COV_XCD
-#define DISCO_COV_XCD 8               // XCDs the workgroup ids are dealt over (0: plain tile-fastest ids)
-#endif
 #ifndef DISCO_COV_LDS_WPE
 #define DISCO_COV_LDS_WPE 3           // waves per SIMD the register allocation leaves room for
 #endif
@@ -970,26 +942,17 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__((64 * cov_split_waves<KR, SKIPLO
     __shared__ CovStage<M, KR, DISCO_COV_STAGE_FRAMES> sh[2];
     const int nbin = a.F - 1, tiles = nbin / 64;          // the launcher checks nbin % 64 == 0
     // Which workgroup does what: the Kl nodes of a room read the same K - 1 remote rows of a (tile, chunk), so they are made
-    // NEIGHBOURS ON ONE XCD (one L2): the hardware deals consecutive workgroup ids round-robin to the 8 XCDs, hence id b is
-    // logical item (b % 8) * (grid / 8) + b / 8, and logical items run node-fastest.  (Tile-fastest ids, as k_cov_split's,
-    // spread the 8 nodes of a room over 8 L2s and every remote row crosses the fabric up to K - 1 times.)
-#if DISCO_COV_XCD
+    // NEIGHBOURS ON ONE XCD (xcd_item, common.h): logical items run node-fastest.  (Tile-fastest ids, as k_cov_split's, spread the 8
+    // nodes of a room over 8 L2s and every remote row crosses the fabric up to K - 1 times.)
     const long long n_items = (long long)a.R * a.Kl * (tiles + 1) * a.chunks;
-    long long item = (long long)(blockIdx.x % DISCO_COV_XCD) * (gridDim.x / DISCO_COV_XCD) + blockIdx.x / DISCO_COV_XCD;
-    if (item >= n_items) return;                           // the grid is padded to a multiple of 8
+    long long item = xcd_item();
+    if (item >= n_items) return;
     const int kl = (int)(item % a.Kl);
     item /= a.Kl;
     const int c = (int)(item % a.chunks);
     item /= a.chunks;
     const int tile = (int)(item % (tiles + 1));
     const long long g = (item / (tiles + 1)) * a.Kl + kl;
-#else
-    int bid = blockIdx.x;
-    const int c = bid % a.chunks;
-    bid /= a.chunks;
-    const int tile = bid % (tiles + 1);
-    const long long g = bid / (tiles + 1);
-#endif
     const int lane = threadIdx.x & 63;
     const int wid = wave_id();
     const int role = wid + (KR > 0 ? 0 : 6);               // (as in k_cov_split: without remote rows only the local block's two roles exist)

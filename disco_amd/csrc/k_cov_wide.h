@@ -18,9 +18,6 @@
 namespace disco {
 
 constexpr int CW_GRP = 4, CW_WAVES = 4, CW_PMAX = 32;
-#ifndef DISCO_COV_WIDE_XCD
-#define DISCO_COV_WIDE_XCD 8
-#endif
 
 __host__ __device__ constexpr int cov_wide_groups(int P) { return (P + CW_GRP - 1) / CW_GRP; }
 __host__ __device__ constexpr int cov_wide_blocks(int P) { return cov_wide_groups(P) * (cov_wide_groups(P) + 1) / 2; }
@@ -128,13 +125,13 @@ __device__ __forceinline__ void cov_wide_wave(const CovArgs& a, int M, int KR, l
 }
 
 // grid: n_items = R * Kl * (tiles + 1) * chunks * nbg logical items (nbg = ceil(blocks / CW_WAVES)), padded to a multiple of
-// DISCO_COV_WIDE_XCD; block = 64 * CW_WAVES threads, wave w of item bg takes block bg * CW_WAVES + w
+// N_XCD (xcd_item, common.h); block = 64 * CW_WAVES threads, wave w of item bg takes block bg * CW_WAVES + w
 template <bool SAMEZ>
 __global__ __launch_bounds__(64 * CW_WAVES) void k_cov_wide(CovArgs a, int M, int KR) {
     const int P = M + KR, ng = cov_wide_groups(P), nblk = cov_wide_blocks(P), nbg = (nblk + CW_WAVES - 1) / CW_WAVES;
     const int tiles = (a.F - 1 + 63) / 64;
     const long long n_items = a.R * a.Kl * (long long)(tiles + 1) * a.chunks * nbg;
-    long long item = (long long)(blockIdx.x % DISCO_COV_WIDE_XCD) * (gridDim.x / DISCO_COV_WIDE_XCD) + blockIdx.x / DISCO_COV_WIDE_XCD;
+    long long item = xcd_item();
     if (item >= n_items) return;
     const int bg = (int)(item % nbg);
     item /= nbg;

@@ -34,42 +34,30 @@ struct Step2Geom {
     bool nyq;
 };
 
-// DISCO_S2_XCD_MAP: which workgroup does what (a pure permutation: every sum keeps its operands and its order).
-//   0  blockIdx.x = (room, tile, chunk), chunk fastest: the tiles + 1 workgroups of one (room, chunk) are `chunks` apart and land on as many
-//      XCDs (workgroups go round the 8 XCDs in turn)
-//   1  units (room, chunk) in groups of 8; inside a group blockIdx.x = (tile, unit), unit fastest: the tiles + 1 workgroups of a unit are 8
-//      apart -- dispatched together and on ONE XCD, so the lines they share (the mask spans that straddle two tiles, the Nyquist
-//      workgroup's lines) can meet in that XCD's L2.  The last, incomplete group keeps the order (tile, unit) without the alignment.
-//      C3, k_step2_cov_fused<4, 4, true> on packed rows: 25.00 -> 24.61 GB fetched, 4.27 -> 4.14 ms (profiles/s2_xcd_map.txt)
-#ifndef DISCO_S2_XCD_MAP
-#define DISCO_S2_XCD_MAP 1
-#endif
+// Which workgroup does what (a pure permutation: every sum keeps its operands and its order): units (room, chunk) in groups of 8; inside
+// a group blockIdx.x = (tile, unit), unit fastest: the tiles + 1 workgroups of a unit are 8 apart -- dispatched together and on ONE XCD
+// (workgroups go round the 8 XCDs in turn), so the lines they share (the mask spans that straddle two tiles, the Nyquist workgroup's lines)
+// can meet in that XCD's L2.  The last, incomplete group keeps the order (tile, unit) without the alignment.  Against plain
+// (room, tile, chunk) ids, C3, k_step2_cov_fused<4, 4, true> on packed rows: 25.00 -> 24.61 GB fetched, 4.27 -> 4.14 ms (profiles/s2_xcd_map.txt)
 __device__ __forceinline__ Step2Geom step2_geom(const Step2Args& a, int lane) {
     Step2Geom g;
     const int nbin = a.F - 1, tiles = nbin / 64;
-    int bid = blockIdx.x;
+    const int bid = blockIdx.x;
     int tile;
-    if (DISCO_S2_XCD_MAP) {
-        const long long units = (long long)(gridDim.x / (tiles + 1));           // rooms * chunks
-        const long long full = units / 8, grp = bid / (8 * (tiles + 1));
-        long long u;
-        if (grp < full) {
-            const int j = bid % (8 * (tiles + 1));
-            tile = j / 8;
-            u = grp * 8 + j % 8;
-        } else {
-            const int n = (int)(units - full * 8), j = (int)(bid - full * 8 * (tiles + 1));
-            tile = j / n;
-            u = full * 8 + j % n;
-        }
-        g.c = (int)(u % a.chunks);
-        g.r = u / a.chunks;
+    const long long units = (long long)(gridDim.x / (tiles + 1));           // rooms * chunks
+    const long long full = units / 8, grp = bid / (8 * (tiles + 1));
+    long long u;
+    if (grp < full) {
+        const int j = bid % (8 * (tiles + 1));
+        tile = j / 8;
+        u = grp * 8 + j % 8;
     } else {
-        g.c = bid % a.chunks;
-        bid /= a.chunks;
-        tile = bid % (tiles + 1);
-        g.r = bid / (tiles + 1);
+        const int n = (int)(units - full * 8), j = (int)(bid - full * 8 * (tiles + 1));
+        tile = j / n;
+        u = full * 8 + j % n;
     }
+    g.c = (int)(u % a.chunks);
+    g.r = u / a.chunks;
     g.t0 = (int)(((long long)a.T * g.c) / a.chunks);
     g.t1 = (int)(((long long)a.T * (g.c + 1)) / a.chunks);
     g.nyq = tile == tiles;
@@ -361,10 +349,6 @@ __device__ __forceinline__ void ola_zero_segments(float* __restrict__ og, int s0
     for (long long pos = p0 + lane; pos < p1; pos += 64) og[pos] = 0.f;
 }
 
-#ifndef DISCO_AI_PREFETCH
-#define DISCO_AI_PREFETCH 1
-#endif
-
 template <int N, int M, int K>
 struct alignas(16) ApplyIstftShared {
     c32 buf[K][fft_buf_len<N>()];
@@ -416,7 +400,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * K, (M <= 4 && K <= 4) ? 2 :
 #pragma unroll
     for (int e = 0; e < EH; ++e) carry[e] = 0.f;
     float* og = out + g * (long long)L;
-    constexpr bool PF = DISCO_AI_PREFETCH && M <= 4 && K <= 4;     // larger shapes have no registers to spare for it
+    constexpr bool PF = M <= 4 && K <= 4;     // larger shapes have no registers to spare for it
     // The kernel runs 2 waves per SIMD (LDS- and register-bound) and measured 32 % VALU-busy: latency-bound.  The frame
     // pair's spectra are therefore fetched one pair AHEAD, raw and unconditionally (frame index clamped), into registers
     // that are dead during the inverse FFT, and pinned (DISCO_CONSUME) before the pair's output stores are issued.
@@ -577,9 +561,6 @@ struct alignas(16) ApplyIstftWideShared {
     float4 nyq[WF][NL];
     c32 wn[M + KR + 1];
 };
-#ifndef DISCO_WIDE_EXP
-#define DISCO_WIDE_EXP 0                                // TIMING-ONLY builds: bit 0 no transform / overlap-add, 1 no filter arithmetic, 2 no loads (garbage results)
-#endif
 template <int N, int M, int KR>
 __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) void k_apply_istft_wide(ApplyIstftWideArgs a, const float* __restrict__ win,
                                                                                                      const c32* __restrict__ tw) {
@@ -592,7 +573,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
     const int wv = wave_id(), lane = threadIdx.x & 63;
     const int T = a.T;
     const long long n_items = a.R * a.Kl * (long long)a.chunks;
-    long long item = (long long)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;
+    long long item = xcd_item();
     if (item >= n_items) return;
     const int kl = (int)(item % a.Kl);
     item /= a.Kl;
@@ -655,7 +636,6 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
         float q[2][MH][4];                              // (scalars on purpose, see k_apply_mq)
         c32 zq[2][KR];
         auto fetch = [&](int pr, int u, int fr) {
-            if (DISCO_WIDE_EXP & 4) return;
             const long long tF = (long long)min(frame_of(pr, u, fr), T - 1) * F;   // frames past the signal: clamped (finite) data, zeroed at the ring
 #pragma unroll
             for (int q_ = 0; q_ < MH; ++q_) {
@@ -681,7 +661,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
             c32(*ring)[F + 1] = sh.ring[pr & 1];
             const int tn = frame_of(pr, wv / 2, wv & 1);
             float nv[4] = {0.f, 0.f, 0.f, 0.f};
-            if (n_ld && !(DISCO_WIDE_EXP & 4)) {
+            if (n_ld) {
                 const float* p_ = n_src + (long long)min(tn, T - 1) * n_stride;
                 if (n_isx) {
                     const float4 v = *reinterpret_cast<const float4*>(p_);
@@ -717,20 +697,15 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
                     }
                     DISCO_LDS_RAW();
                     float ar = 0.f, ai = 0.f;
-                    if (!(DISCO_WIDE_EXP & 2)) {
 #pragma unroll
-                        for (int i = 0; i < M; ++i) {
-                            ar = fmaf(wl[i].x, x[i].x, fmaf(-wl[i].y, x[i].y, ar));
-                            ai = fmaf(wl[i].x, x[i].y, fmaf(wl[i].y, x[i].x, ai));
-                        }
+                    for (int i = 0; i < M; ++i) {
+                        ar = fmaf(wl[i].x, x[i].x, fmaf(-wl[i].y, x[i].y, ar));
+                        ai = fmaf(wl[i].x, x[i].y, fmaf(wl[i].y, x[i].x, ai));
+                    }
 #pragma unroll
-                        for (int jj = 0; jj < KR; ++jj) {
-                            ar = fmaf(wr[jj].x, z[jj].x, fmaf(-wr[jj].y, z[jj].y, ar));
-                            ai = fmaf(wr[jj].x, z[jj].y, fmaf(wr[jj].y, z[jj].x, ai));
-                        }
-                    } else {
-                        ar = x[0].x + z[0].x;
-                        ai = x[M - 1].y + z[KR - 1].y;
+                    for (int jj = 0; jj < KR; ++jj) {
+                        ar = fmaf(wr[jj].x, z[jj].x, fmaf(-wr[jj].y, z[jj].y, ar));
+                        ai = fmaf(wr[jj].x, z[jj].y, fmaf(wr[jj].y, z[jj].x, ai));
                     }
                     const int t = frame_of(pr, u, fr);
                     const c32 yv = t < Tr ? make_float2(ar, ai) : make_float2(0.f, 0.f);
@@ -778,7 +753,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
             __syncthreads();                            // the filter waves have completed ring pr & 1
             const c32(*ring)[F + 1] = sh.ring[pr & 1];
             const int tA = s0 + 2 * pr;
-            if (tA - 1 < T && !(DISCO_WIDE_EXP & 1)) {  // (wave-uniform) else: a run past the signal's end, nothing left to emit
+            if (tA - 1 < T) {                           // (wave-uniform) else: a run past the signal's end, nothing left to emit
                 c32 yf[2][NJ];
 #pragma unroll
                 for (int fr = 0; fr < 2; ++fr) {
@@ -825,31 +800,22 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * (N / 128 + N / 256), 1) voi
 // pass is pure wave-local arithmetic (M/2 forward transforms per frame, one inverse per frame pair, no workgroup barrier).
 // A wave owns `pairs` frame pairs of one node (2 pairs - 1 hop segments; consecutive waves overlap by one frame, as in
 // k_step2_apply_istft); the half-window shared by consecutive frames is recycled in registers as in k_stft.
-// DISCO_SAI_EXP (default 0): TIMING-ONLY builds of k_stft_apply_istft -- bit 0 no forward transforms (the filter takes the windowed samples),
-// 1 no inverse transform, 2 no output stores, 3 no sample loads; results are garbage (profiles/r05_h_stft_parts.txt)
-#ifndef DISCO_SAI_EXP
-#define DISCO_SAI_EXP 0
-#endif
-// DISCO_SAI_TAPS_LDS (default 1): the node's filter -- (N/2 + 1) x M taps, 40 registers per lane for a 512-point, 4-mic node -- sits in a
-// wave-private LDS block [pair][bin] (one conflict-free ds_read_b128 per channel pair and bin) instead of registers: 198 -> under 168 registers,
-// THREE waves per SIMD instead of two.  The pass is bound by the latency of its loads and of its transforms at two waves per SIMD
+// The node's filter -- (N/2 + 1) x M taps, 40 registers per lane for a 512-point, 4-mic node -- sits in a wave-private LDS block
+// [pair][bin] (one conflict-free ds_read_b128 per channel pair and bin), not in registers: 198 -> under 168 registers, THREE waves per SIMD
+// instead of two.  The pass is bound by the latency of its loads and of its transforms at two waves per SIMD
 // (profiles/r05_h_stft_parts.txt), so the third wave is what pays.
-#ifndef DISCO_SAI_TAPS_LDS
-#define DISCO_SAI_TAPS_LDS 1
-#endif
 template <int N, int CHP>
 struct alignas(16) StftApplyShared {
     c32 buf[STFT_WAVES][fft_buf_len<N>()];
-    float4 taps[DISCO_SAI_TAPS_LDS ? STFT_WAVES : 1][DISCO_SAI_TAPS_LDS ? CHP : 1][DISCO_SAI_TAPS_LDS ? N / 2 + 1 : 1];
+    float4 taps[STFT_WAVES][CHP][N / 2 + 1];
 };
 template <int N, int M>
-__global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO_SAI_TAPS_LDS ? 3 : 2) : 1) void k_stft_apply_istft(const float* __restrict__ x, const c32* __restrict__ wf,
+__global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? 3 : 1) void k_stft_apply_istft(const float* __restrict__ x, const c32* __restrict__ wf,
                                                                                     float* __restrict__ out, const float* __restrict__ win,
                                                                                     const c32* __restrict__ tw, int L, int T, int pad_mode,
                                                                                     int runs_per_node, int pairs, long long n_witems,
                                                                                     const int* __restrict__ lens, int sig_per_room) {
     constexpr int E = FftPlan<N>::E, F = N / 2 + 1, H = N / 2, EH = E / 2, NJ = EH + 1, CHP = (M + 1) / 2;
-    constexpr bool TL = DISCO_SAI_TAPS_LDS != 0;
     __shared__ StftApplyShared<N, CHP> sh;
     const int wave = wave_id(), lane = threadIdx.x & 63;
     const long long item = (long long)blockIdx.x * STFT_WAVES + wave;
@@ -867,29 +833,16 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
     wtw.init(tw, lane);
     float w[E];
     load_window<N>(w, win, lane);
-    // the node's filter at this lane's bins (f = lane + 64 j; lane 0: Nyquist too), at half weight: the forward transforms below run on
+    // the node's filter -> the wave's LDS block (lane l stages bins l, l + 64, ...), at half weight: the forward transforms below run on
     // the full-weight window (it is the synthesis window too), so the untangled spectra are 2 X (fft.h: rfft_pair_untangle leaves the
     // division by two to its caller); exact
-    c32 wg[TL ? 1 : NJ][TL ? 1 : M];
-    if constexpr (TL) {
-        for (int f = lane; f < F; f += 64)
+    for (int f = lane; f < F; f += 64)
 #pragma unroll
-            for (int p = 0; p < CHP; ++p) {
-                const c32 a = wf[(g * F + f) * M + 2 * p], b = (2 * p + 1 < M) ? wf[(g * F + f) * M + 2 * p + 1] : make_float2(0.f, 0.f);
-                sh.taps[wave][p][f] = make_float4(0.5f * a.x, 0.5f * a.y, 0.5f * b.x, 0.5f * b.y);
-            }
-        DISCO_LDS_RAW();                             // wave-private block: the wave's own writes are in place
-    } else {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = (j < EH) ? lane + 64 * j : F - 1;
-#pragma unroll
-            for (int i = 0; i < M; ++i) {
-                const c32 wv = wf[(g * F + f) * M + i];
-                wg[j][i] = make_float2(0.5f * wv.x, 0.5f * wv.y);
-            }
+        for (int p = 0; p < CHP; ++p) {
+            const c32 a = wf[(g * F + f) * M + 2 * p], b = (2 * p + 1 < M) ? wf[(g * F + f) * M + 2 * p + 1] : make_float2(0.f, 0.f);
+            sh.taps[wave][p][f] = make_float4(0.5f * a.x, 0.5f * a.y, 0.5f * b.x, 0.5f * b.y);
         }
-    }
+    DISCO_LDS_RAW();                                 // wave-private block: the wave's own writes are in place
     const float* xa[CHP];
     const float* xb[CHP];
 #pragma unroll
@@ -914,32 +867,18 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
             const int t = tA + fr;
             c32 nxt[CHP][EH];                        // the next frame's new half-window, in flight under this frame's transforms
 #pragma unroll
-            for (int p = 0; p < CHP; ++p) {
-                if (DISCO_SAI_EXP & 8) {
-#pragma unroll
-                    for (int e = 0; e < EH; ++e) nxt[p][e] = make_float2(0.25f * e + lane, 1.f);
-                } else {
-                    load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], min(t + 1, Tr - 1), Lr, pad_mode, lane);
-                }
-            }
+            for (int p = 0; p < CHP; ++p) load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], min(t + 1, Tr - 1), Lr, pad_mode, lane);
 #pragma unroll
             for (int j = 0; j < NJ; ++j) yf[fr][j] = make_float2(0.f, 0.f);
 #pragma unroll
             for (int p = 0; p < CHP; ++p) {
                 c32 v[E];
                 apply_window<N>(v, raw[p], w, 2 * p + 1 < M);
-                if (!(DISCO_SAI_EXP & 1)) fft_wave<N>(v, wtw, buf, lane);
+                fft_wave<N>(v, wtw, buf, lane);
                 rfft_pair_untangle<N>(v, buf, lane, [&](int j, int f, c32 a, c32 b) {
                     // yf += conj(w_2p) X_2p + conj(w_2p+1) X_2p+1
-                    c32 wa, wb;
-                    if constexpr (TL) {
-                        const float4 t4 = sh.taps[wave][p][f];
-                        wa = make_float2(t4.x, t4.y);
-                        wb = make_float2(t4.z, t4.w);
-                    } else {
-                        wa = wg[j][2 * p];
-                        wb = wg[j][2 * p + 1 < M ? 2 * p + 1 : 2 * p];
-                    }
+                    const float4 t4 = sh.taps[wave][p][f];
+                    const c32 wa = make_float2(t4.x, t4.y), wb = make_float2(t4.z, t4.w);
                     c32 acc = cfma_conj(wa, a, yf[fr][j]);
                     if (2 * p + 1 < M) acc = cfma_conj(wb, b, acc);
                     yf[fr][j] = acc;
@@ -962,10 +901,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, M <= 4 ? (DISCO
         // ---- V = A~ + i B~ (Hermitian extensions of the two filtered frames), conjugated for the inverse-by-forward trick
         c32 v[E];
         irfft_pair_pack<N>(yf[0], yf[1], v, lane);       // cross-lane, no LDS round trip (fft.h)
-        if (!(DISCO_SAI_EXP & 2)) fft_wave<N>(v, wtw, buf, lane);
+        fft_wave<N>(v, wtw, buf, lane);
         // ---- window, overlap-add: segment (tA-1) = carry + A[lo], segment tA = A[hi] + B[lo], carry <- B[hi]
-        if (!(DISCO_SAI_EXP & 4)) ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, Tr, Lr, T, L, lane);
-        else if (v[0].x == 123456.f) og[lane] = v[1].y;     // (keeps the arithmetic alive)
+        ola_emit_pair<N>(v, carry, ow, og, win, tA, pr == 0, Tr, Lr, T, L, lane);
     }
 }
 

@@ -69,12 +69,7 @@ struct RoomArgs {
 // asm: hipcc's own LDS-DMA tracking would wait for vmcnt(0) before every LDS read, the ring index being a run-time value); every
 // iteration waits for everything it issued, so nothing depends on the order in which loads and stores retire.  build.py refuses the
 // kernel beyond 64 bytes of scratch per lane (a few per-lane loader constants reloaded per iteration; the accumulators must stay in registers).
-#ifndef DISCO_ROOM_EXP
-#define DISCO_ROOM_EXP 0
-#endif
-#ifndef DISCO_ROOM_DEPTH
-#define DISCO_ROOM_DEPTH 6              // ring slots: two groups per iteration, issued two iterations ahead
-#endif
+constexpr int ROOM_DEPTH = 6;         // ring slots: two groups per iteration, issued two iterations ahead (the slot arithmetic below is written for 6)
 
 template <int M, int K, int SUB_>
 struct RoomGeomS {
@@ -101,9 +96,9 @@ struct RoomGeomS {
 template <int M, int K, int SUB>
 struct alignas(16) RoomRingS {
     using Gm = RoomGeomS<M, K, SUB>;
-    float4 xs[DISCO_ROOM_DEPTH][Gm::NITEMS];           // granules, linear in the loader's item index
+    float4 xs[ROOM_DEPTH][Gm::NITEMS];                 // granules, linear in the loader's item index
     float4 wt[2][Gm::NTAPP];                           // the step-1 filters of the current and of the next item, as granules
-    float ms[DISCO_ROOM_DEPTH][Gm::NMW][64 + 8];       // one padded row per wave-load (the SUB sub-chunks of a wave read different rows)
+    float ms[ROOM_DEPTH][Gm::NMW][64 + 8];             // one padded row per wave-load (the SUB sub-chunks of a wave read different rows)
     c32 zs[4][SUB][K + 1][Gm::NB];                     // z of four groups in flight; the + 1 row keeps the sub-chunks of a wave off each other's banks
 };
 
@@ -191,9 +186,8 @@ template <int M, int K, int SUB, bool IS_A>
 __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M, K, SUB>& sh) {
     using Gm = RoomGeomS<M, K, SUB>;
     constexpr int KR = Gm::KR, P = Gm::P, NP = Gm::NP, NB = Gm::NB, NA = Gm::NA, WA = Gm::WA, NT = Gm::NT, MH = Gm::MH;
-    constexpr int NROW = Gm::NROW, NITEMS = Gm::NITEMS, NL = Gm::NL, D = DISCO_ROOM_DEPTH, BPR = Gm::BPR, LH = Gm::LH;
+    constexpr int NROW = Gm::NROW, NITEMS = Gm::NITEMS, NL = Gm::NL, D = ROOM_DEPTH, BPR = Gm::BPR, LH = Gm::LH;
     constexpr int LOGM = M == 8 ? 3 : 2;
-    static_assert(D == 6, "two groups per iteration, two iterations ahead");
     static_assert(M == 8 || M == 4, "byte offsets of z are derived from those of X by a shift");
     const int T = a.T, F = a.F;
     const unsigned FM8 = (unsigned)(F * M * 8);
@@ -471,31 +465,23 @@ __device__ __forceinline__ void room_cov_dma_run(const RoomArgs& a, RoomRingS<M,
     int s0 = 0, zb0 = 0;                                // ring slot / z buffer of the fold position's first group
     int rp = rd, fp = fd;                               // the item whose last groups were folded in the previous iteration (pending)
     bool pending = false;
-    // DISCO_ROOM_EXP (default 0): TIMING-ONLY builds with parts of the loop body removed -- bit 0 the folds, 1 the z formation, 2 the loads,
-    // 3 the barrier, 4 the wait for the loads (raw s_barrier); the results are garbage (tools/gpu/mk_variant.sh roomexp1 "-DDISCO_ROOM_EXP=1" api_room_s8; profiles/r04_u_room_parts.txt)
     while (true) {
-        if (vi && !(DISCO_ROOM_EXP & 4)) {
+        if (vi) {
             if (ji == 0) issue_taps(ri, fi, ni & 1);    // (the form position left that buffer's item an iteration ago)
             issue(ri, fi, 2 * ji, (s0 + 4) % D, Ti);
             issue(ri, fi, 2 * ji + 1, (s0 + 5) % D, Ti);
         }
         if (pending) finish(rp, fp);
-        if (vf && !(DISCO_ROOM_EXP & 2)) {
+        if (vf) {
             form_z(rf, ff, 2 * jf, (s0 + 2) % D, zb0 ^ 2, nf & 1, Tf);
             form_z(rf, ff, 2 * jf + 1, (s0 + 3) % D, (zb0 ^ 2) + 1, nf & 1, Tf);
         }
-        if (!(DISCO_ROOM_EXP & 1)) {
-            fold(fd, 2 * jd, s0, zb0, Td);
-            fold(fd, 2 * jd + 1, (s0 + 1) % D, zb0 + 1, Td);
-        }
+        fold(fd, 2 * jd, s0, zb0, Td);
+        fold(fd, 2 * jd + 1, (s0 + 1) % D, zb0 + 1, Td);
         pending = jd == J - 1;
         rp = rd, fp = fd;
-#if DISCO_ROOM_EXP & 16
-        __builtin_amdgcn_s_barrier();                  // (bit 4: the loads are never waited for, raw barrier: is the loop waiting for them?)
-#else
         vm_wait_all();
-        if (!(DISCO_ROOM_EXP & 8)) __syncthreads();
-#endif
+        __syncthreads();
         if (!vf) break;                                 // the fold position was this workgroup's last iteration
         s0 = (s0 + 2) % D;
         zb0 ^= 2;

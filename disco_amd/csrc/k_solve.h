@@ -24,9 +24,6 @@
 
 namespace disco {
 
-#ifndef DISCO_SOLVE_PACKED
-#define DISCO_SOLVE_PACKED 1
-#endif
 // Squaring stops with the square whose tau = tr(B^2) came within DISCO_SQUARING_DONE of 1: 1 - tau ~ 2 rho (rho = the
 // sub-dominant weight (d1/d0)^(2^k) of the matrix that was squared), so the square that is kept carries rho^2 < 0.017.  The
 // rest of the way is covered by DISCO_POWER_STEPS power steps v <- B v on the column picked from it: each costs 1/P of a
@@ -97,8 +94,8 @@ struct SolveGeom {
     static constexpr int YW = (P % 8 == 0) ? P + 1 : P;     // row pitch of Y: padded only where P * 16 B would alias LDS banks
     // (+1 where that count is even: the per-problem stride in 16-byte words is then odd, so the 4 / 8 / 16 problems a wave serves
     // start on distinct bank groups and a broadcast read of "the same entry of every problem" is conflict-free)
-    static constexpr int LSZ = (DISCO_SOLVE_PACKED ? P * (P + 1) / 2 : P * (P + 1)) | 1;
-    __host__ __device__ static constexpr int lt(int i, int k) { return DISCO_SOLVE_PACKED ? i * (i + 1) / 2 + k : i * (P + 1) + k; }
+    static constexpr int LSZ = (P * (P + 1) / 2) | 1;
+    __host__ __device__ static constexpr int lt(int i, int k) { return i * (i + 1) / 2 + k; }
 };
 
 // Where the pencils come from: either full row-major matrices (the disco_gevd_mwf_r1 ABI) or, inside the fused

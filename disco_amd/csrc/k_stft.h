@@ -502,43 +502,33 @@ namespace disco {
 // ---- STFT + step-1 covariance in one pass over the samples ---------------------------------------------------
 // tango.py:335 + 357-364: the spectra are needed twice right away (stored for step 2, and reduced into the local
 // covariances), so the 4 waves of a workgroup stream 4 interleaved runs of frames of one node, park each
-// frame's M-channel spectrum in an LDS tile, and after a barrier the workgroup switches to one-thread-per-bin:
-// every thread copies its bin's M-vector to X (coalesced 8*M*64-byte wave stores) and folds it into the
+// frame's transforms (one per channel pair) in an LDS tile, and after a barrier the workgroup switches to one-thread-per-bin:
+// every thread copies its share of the frame to X (coalesced 16-byte-per-lane wave stores) and folds its bin's M-vector into the
 // P(P+1)/2 covariance accumulators it keeps in registers for the whole run.  Saves the separate covariance
 // pass over X (8*M*F bytes per node-frame).
 // frames per wave per workgroup are a launch parameter (`runw`; a workgroup covers 4 * runw frames): long runs amortise the
 // first-frame load and the partial-sum write-out (80 is best at C3), short ones keep small batches spread over the chip
 
-// ZPITCH: pitch of a pair plane in the Z layout (DISCO_ZTILE below): N + 16 complex, i.e. consecutive planes start 32 banks apart, so the
-// copy-out's ds_read_b64 -- consecutive lanes alternate between the planes of one bin -- never meet on a bank
+// The tile holds Z planes: the transform waves park the raw pair spectra Z (natural order, one conflict-free ds_write_b64 per slot) and
+// whoever picks a bin up separates the two channels himself -- A = Z[f] + conj Z[N - f], B = -i (Z[f] - conj Z[N - f]): the very operations
+// of rfft_pair_untangle on the very operands, so every spectrum and every sum is bit for bit what a tile of untangled rows would give.
+// Against such a tile it saves, per transform, the 2 E ds_bpermute of the untangle and E/2 ds_write_b128 at a 32-byte pitch: ~280 -> ~180
+// LDS cycles on the pipe that, with the VALU, bounds the STORE = false variant (profiles/r03_q_C2x4000_pmc_alu.json), and the untangle's
+// registers in the phase that sets this kernel's register count.  (A swizzled tile like k_stft_pairs' was measured 8 % slower here.)
+// ZPITCH: pitch of a pair plane: N + 16 complex, i.e. consecutive planes start 32 banks apart, so the copy-out's ds_read_b64 --
+// consecutive lanes alternate between the planes of one bin -- never meet on a bank
 template <int N>
 constexpr int stft_cov_zpitch() { return N + 16; }
-template <int N, int CHP, bool ZT>
+template <int N, int CHP>
 struct alignas(16) StftCovShared {
     c32 buf[STFT_WAVES][fft_buf_len<N>()];
-    c32 tile[STFT_WAVES][ZT ? CHP * stft_cov_zpitch<N>() : (N / 2 + 1) * 2 * CHP];
+    c32 tile[STFT_WAVES][CHP * stft_cov_zpitch<N>()];
 };
 
 // 3 waves per SIMD (<= 168 VGPRs) is reachable for the common 512-point, M <= 4 shape and worth ~3 %; larger shapes keep
 // whatever occupancy their register need allows
 #ifndef DISCO_SC_WPE
 #define DISCO_SC_WPE 3
-#endif
-// DISCO_ZTILE: the transform waves park the raw pair spectra Z (natural order, one conflict-free ds_write_b64 per slot) and whoever picks
-// a bin up separates the two channels himself -- A = Z[f] + conj Z[N - f], B = -i (Z[f] - conj Z[N - f]): the very operations of
-// rfft_pair_untangle on the very operands, so every spectrum and every sum is bit for bit what the untangled tile gives.  What it saves
-// sits on the LDS pipe, which together with the VALU bounds the STORE = false variant (profiles/r03_q_C2x4000_pmc_alu.json: ~48 % busy
-// each, barely overlapped) -- per transform the 2 E ds_bpermute of the untangle (an LDS store + load each) and E/2 ds_write_b128 at a
-// 32-byte pitch (13 cycles each, MI355X_MICROARCH.md "LDS") against E ds_write_b64 (6 each): ~280 -> ~180 LDS cycles per transform --
-// and the untangle's registers in the transform phase, the phase that sets this kernel's register count.
-#ifndef DISCO_ZTILE
-#define DISCO_ZTILE 1
-#endif
-// DISCO_SC_EXP (default 0): TIMING-ONLY builds of k_stft_cov with parts of the frame loop removed -- bit 0 the transforms (window, FFT, tile
-// write), 1 the covariance fold, 2 the X store, 3 the sample and mask loads; results are garbage, only the time counts
-// (tools/gpu/mk_variant.sh scexp<N> "-DDISCO_SC_EXP=<N>" api_stft_cov; profiles/r05_h_stft_parts.txt)
-#ifndef DISCO_SC_EXP
-#define DISCO_SC_EXP 0
 #endif
 // STORE = false: the spectra are reduced into the covariances and dropped (single-node path: the filter pass recomputes them
 // from the samples, k_stft_apply_istft, instead of reading 8 M F bytes per node-frame back)
@@ -557,11 +547,9 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
     constexpr int NP = M * (M + 1) / 2;
     constexpr int FX = PACK ? F - 1 : F;           // bins of a stored row
     constexpr int BPT = (F - 1) / 256;             // bins per thread: 1 (N = 512) or 2 (N = 1024)
-    constexpr bool ZT = DISCO_ZTILE != 0;
     constexpr int ZP = stft_cov_zpitch<N>();
-    __shared__ StftCovShared<N, CHP, ZT> sh;
-    // X layout: row (frame of wave ww, bin f) = the 2 CHP channels as they go to HBM; Z layout: plane (ww, pair p) = Z[0 .. N)
-    auto xrow = [&](int ww, int f) { return &sh.tile[ww][f * 2 * CHP]; };
+    __shared__ StftCovShared<N, CHP> sh;
+    // plane (frame of wave ww, pair p) = Z[0 .. N)
     auto zplane = [&](int ww, int p) { return &sh.tile[ww][p * ZP]; };
     const int tid = threadIdx.x, wave = wave_id(), lane = tid & 63;
     const long long g = blockIdx.x / chunks;
@@ -634,39 +622,24 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
         for (int ww = 0; ww < STFT_WAVES; ++ww) {
             const int t2 = min(tb + ww * runw + it, Tr - 1);         // clamped: unconditional loads, used only when valid
 #pragma unroll
-            for (int b = 0; b < BPT; ++b) mv[ww][b] = (DISCO_SC_EXP & 8) ? 0.5f : mg[(long long)t2 * F + tid + 256 * b];
-            mny[ww] = (DISCO_SC_EXP & 8) ? 0.5f : mg[(long long)t2 * F + F - 1];
+            for (int b = 0; b < BPT; ++b) mv[ww][b] = mg[(long long)t2 * F + tid + 256 * b];
+            mny[ww] = mg[(long long)t2 * F + F - 1];
         }
         c32 nxt[CHP][EH];
         {
             const int tn = min(t + 1, Tr - 1);             // clamped: harmless reload at the end of a run
 #pragma unroll
-            for (int p = 0; p < CHP; ++p) {
-                if (DISCO_SC_EXP & 8) {
-#pragma unroll
-                    for (int e = 0; e < EH; ++e) nxt[p][e] = make_float2(0.25f * e + lane, 1.f);
-                } else {
-                    load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, Lr, pad_mode, lane);
-                }
-            }
+            for (int p = 0; p < CHP; ++p) load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, Lr, pad_mode, lane);
         }
-        if (valid && !(DISCO_SC_EXP & 1)) {
+        if (valid) {
 #pragma unroll
             for (int p = 0; p < CHP; ++p) {
                 c32 v[E];
                 apply_window<N>(v, raw[p], w, 2 * p + 1 < M);
                 fft_wave<N>(v, wtw, sh.buf[wave], lane);
-                if constexpr (ZT) {
-                    c32* zp = zplane(wave, p);
+                c32* zp = zplane(wave, p);
 #pragma unroll
-                    for (int e = 0; e < E; ++e) zp[lane + 64 * e] = v[e];
-                } else {
-                    // (NOT swizzled like k_stft_pairs' tile: measured, the swizzle costs this kernel 8 % -- 7.70 against 7.10 ms per C3 launch;
-                    // its stores are 2-way conflicted at worst and the copy-out below wants the plain linear read)
-                    rfft_pair_untangle<N>(v, sh.buf[wave], lane, [&](int, int f, c32 a, c32 b) {
-                        *reinterpret_cast<float4*>(xrow(wave, f) + 2 * p) = make_float4(a.x, a.y, b.x, b.y);
-                    });
-                }
+                for (int e = 0; e < E; ++e) zp[lane + 64 * e] = v[e];
             }
         }
 #pragma unroll
@@ -685,55 +658,39 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
             const int t2 = tb + ww * runw + it;
             if (t2 < min(Tr, tb + (ww + 1) * runw)) {         // workgroup-uniform
                 c32* Xo = STORE ? X + ((g * T + t2) * (long long)FX) * M : nullptr;
-                if constexpr (STORE && PACK && (M & 1) == 0 && !(DISCO_SC_EXP & 4)) {
+                if constexpr (STORE && PACK && (M & 1) == 0) {
                     // packed rows begin on a line: a plain linear copy of (F - 1) * M / 2 granules; the granules of bin 0 carry the
                     // Nyquist bin's real parts where the (zero) imaginary parts of DC would go
                     float4* dst = reinterpret_cast<float4*>(Xo);
                     for (int i = tid; i < (F - 1) * CHP; i += 64 * STFT_WAVES) {
-                        float4 q4;
-                        if constexpr (ZT) {
-                            const int f = i / CHP, pp = i - f * CHP;
-                            const c32* zp = zplane(ww, pp);
-                            const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
-                            const c32 a = cadd_conj(z, zc), b = csub_conj_mi(z, zc);
-                            q4 = make_float4(a.x, a.y, b.x, b.y);
-                            if (f == 0) {
-                                const c32 zq = zp[N / 2];
-                                q4.y = cadd_conj(zq, zq).x;
-                                q4.w = csub_conj_mi(zq, zq).x;
-                            }
-                        } else {
-                            q4 = reinterpret_cast<const float4*>(xrow(ww, 0))[i];
-                            if (i < CHP) {
-                                const float4 qn = reinterpret_cast<const float4*>(xrow(ww, F - 1))[i];
-                                q4.y = qn.x;
-                                q4.w = qn.z;
-                            }
+                        const int f = i / CHP, pp = i - f * CHP;
+                        const c32* zp = zplane(ww, pp);
+                        const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
+                        const c32 a = cadd_conj(z, zc), b = csub_conj_mi(z, zc);
+                        float4 q4 = make_float4(a.x, a.y, b.x, b.y);
+                        if (f == 0) {
+                            const c32 zq = zp[N / 2];
+                            q4.y = cadd_conj(zq, zq).x;
+                            q4.w = csub_conj_mi(zq, zq).x;
                         }
                         store_stream16(&dst[i], q4);
                     }
-                } else if (STORE && (M & 1) == 0 && !(DISCO_SC_EXP & 4)) {
-                    // even M: the tile row IS the X row (F*M complex, contiguous) -> straight 16-B-per-lane copy, every
-                    // wave store covers 1 KiB of consecutive bytes (a per-bin store would touch each 128-B line twice)
+                } else if (STORE && (M & 1) == 0) {
+                    // even M: the X row is F * CHP granules of 16 bytes, one per lane (granule i = bin i / CHP, pair i % CHP, untangled on
+                    // the way out), so every wave store covers 1 KiB of consecutive bytes (a per-bin store would touch each 128-B line twice)
                     // The rows are 8 * M * F bytes long (8224 for M = 4), so they start 0 / 32 / 64 / 96 bytes into a 128-byte line: the
                     // copy is shifted by that much, every wave store then covers whole lines (PMC: stores that straddle lines
                     // at both ends cost a fill read per partial line, +2.8 GB of reads per C3 launch).
                     float4* dst = reinterpret_cast<float4*>(Xo);
                     const int shift = (int)((reinterpret_cast<unsigned long long>(dst) >> 4) & 7);
-                    if constexpr (ZT) {             // granule i = (bin i / CHP, pair i % CHP): untangled on the way out
-                        for (int i = tid - shift; i < F * CHP; i += 64 * STFT_WAVES)
-                            if (i >= 0) {
-                                const int f = i / CHP, pp = i - f * CHP;
-                                const c32* zp = zplane(ww, pp);
-                                const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
-                                const c32 a = cadd_conj(z, zc), b = csub_conj_mi(z, zc);
-                                store_stream16(&dst[i], make_float4(a.x, a.y, b.x, b.y));
-                            }
-                    } else {
-                        const float4* src = reinterpret_cast<const float4*>(xrow(ww, 0));
-                        for (int i = tid - shift; i < F * M / 2; i += 64 * STFT_WAVES)
-                            if (i >= 0) store_stream16(&dst[i], src[i]);
-                    }
+                    for (int i = tid - shift; i < F * CHP; i += 64 * STFT_WAVES)
+                        if (i >= 0) {
+                            const int f = i / CHP, pp = i - f * CHP;
+                            const c32* zp = zplane(ww, pp);
+                            const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
+                            const c32 a = cadd_conj(z, zc), b = csub_conj_mi(z, zc);
+                            store_stream16(&dst[i], make_float4(a.x, a.y, b.x, b.y));
+                        }
                 }
 #pragma unroll
                 for (int b = 0; b < BPT; ++b) {
@@ -741,16 +698,10 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
                     c32 xv[MP];
 #pragma unroll
                     for (int p = 0; p < CHP; ++p) {
-                        if constexpr (ZT) {
-                            const c32* zp = zplane(ww, p);
-                            const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
-                            xv[2 * p] = cadd_conj(z, zc);
-                            xv[2 * p + 1] = csub_conj_mi(z, zc);
-                        } else {
-                            const float4 q4 = *reinterpret_cast<const float4*>(xrow(ww, f) + 2 * p);
-                            xv[2 * p] = make_float2(q4.x, q4.y);
-                            xv[2 * p + 1] = make_float2(q4.z, q4.w);
-                        }
+                        const c32* zp = zplane(ww, p);
+                        const c32 z = zp[f], zc = zp[(N - f) & (N - 1)];
+                        xv[2 * p] = cadd_conj(z, zc);
+                        xv[2 * p + 1] = csub_conj_mi(z, zc);
                     }
                     if (STORE && (M & 1) != 0) {
                         if (PACK && f == 0) {           // the real parts only: the other half of slot 0 is the Nyquist threads' (below)
@@ -762,32 +713,21 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES, (N == 512 && M 
                         }
                     }
                     const float m = mv[ww][b], mc = 1.f - m;
-                    if (!(DISCO_SC_EXP & 2)) cov_accumulate_shared<M>(xv, m * m, mc * mc, acc_s[b], acc_n[b]);
-                    else acc_s[b][0].x += xv[0].x * m;           // (keeps the tile reads alive)
+                    cov_accumulate_shared<M>(xv, m * m, mc * mc, acc_s[b], acc_n[b]);
                 }
                 // Nyquist bin
                 if (STORE && (M & 1) != 0 && tid < M) {
-                    c32 xq;
-                    if constexpr (ZT) {
-                        const c32 zq = zplane(ww, tid >> 1)[N / 2];
-                        xq = (tid & 1) ? csub_conj_mi(zq, zq) : cadd_conj(zq, zq);
-                    } else {
-                        xq = xrow(ww, F - 1)[tid];
-                    }
+                    const c32 zq = zplane(ww, tid >> 1)[N / 2];
+                    const c32 xq = (tid & 1) ? csub_conj_mi(zq, zq) : cadd_conj(zq, zq);
                     if constexpr (PACK) reinterpret_cast<float*>(Xo)[2 * tid + 1] = xq.x;
                     else Xo[(long long)(F - 1) * M + tid] = xq;
                 }
                 if (tid < 2 * NP) {
                     const float m = (tid & 1) ? 1.f - mny[ww] : mny[ww];
-                    c32 a, b2;
-                    if constexpr (ZT) {             // channel i of the Nyquist bin from its pair's Z[N / 2] (its own partner)
-                        const c32 zi = zplane(ww, ny_i >> 1)[N / 2], zj = zplane(ww, ny_j >> 1)[N / 2];
-                        a = (ny_i & 1) ? csub_conj_mi(zi, zi) : cadd_conj(zi, zi);
-                        b2 = (ny_j & 1) ? csub_conj_mi(zj, zj) : cadd_conj(zj, zj);
-                    } else {
-                        a = xrow(ww, F - 1)[ny_i];
-                        b2 = xrow(ww, F - 1)[ny_j];
-                    }
+                    // channel i of the Nyquist bin from its pair's Z[N / 2] (its own partner)
+                    const c32 zi = zplane(ww, ny_i >> 1)[N / 2], zj = zplane(ww, ny_j >> 1)[N / 2];
+                    const c32 a = (ny_i & 1) ? csub_conj_mi(zi, zi) : cadd_conj(zi, zi);
+                    const c32 b2 = (ny_j & 1) ? csub_conj_mi(zj, zj) : cadd_conj(zj, zj);
                     const float m2 = m * m;
                     acc_ny.x = fmaf(m2, a.x * b2.x + a.y * b2.y, acc_ny.x);
                     if (ny_i != ny_j) acc_ny.y = fmaf(m2, a.y * b2.x - a.x * b2.y, acc_ny.y);

@@ -246,7 +246,7 @@ def test_room_tables_and_staged_step2_restate_the_host_code():
     tables = _read(CSRC, 'dispatch.h')
     assert _table(tables, 'DISCO_FOR_ROOM') == cc.ROOM == rc.ROOM
     assert 'k_room_cov_dma<M_, K_, 8>' in _read(CSRC, 'api_room_s8.hip') and rc.ROOM_SUB == 8
-    assert int(re.search(r'#define DISCO_ROOM_DEPTH (\d+)', _read(CSRC, 'k_room.h')).group(1)) == rc.ROOM_DEPTH
+    assert int(re.search(r'constexpr int ROOM_DEPTH = (\d+);', _read(CSRC, 'k_room.h')).group(1)) == rc.ROOM_DEPTH
     assert len(rc.SPLIT_SHAPES) == 24 and all(8 < M + K - 1 <= cc.CB_PMAX for M, K in rc.SPLIT_SHAPES)
     path = _read(CSRC, 'api_path.hip')
     marks = ['int staged_step2(disco_ctx* ctx,', 'if (same_mask && room_cov_ok(ctx, X, mask_w)) {', 'room_cov_partials(ctx, X, mask_w, w_loc, z, s, store_z)',

@@ -1,6 +1,8 @@
-// Micro-benchmark of the P = 15 covariance kernels (C5 shape) outside the library: build variants with -D flags, time with
-// HIP events.  tools/gpu/kbench/run_cov_bench.py drives it.
+// Micro-benchmark of the P = 15 covariance kernel k_cov_split_lds (C5 shape) outside the library: build variants with -D flags (the
+// numeric knobs of k_cov.h), time with HIP events.  tools/gpu/kbench/run_cov_bench.py drives it.  (`variant` is kept in the signature
+// for the driver; k_cov_split, which variant 0 used to time, is no longer in the library.)
 #include <hip/hip_runtime.h>
+#include "../../../disco_amd/csrc/host.h"
 #include "../../../disco_amd/csrc/k_cov.h"
 using namespace disco;
 
@@ -20,16 +22,13 @@ extern "C" float cov_bench(int variant, const void* X, const void* mask, const v
     a.part = (float4*)part;
     a.K = K; a.T = T; a.F = F; a.chunks = chunks; a.mask_remote = 1; a.Kl = K; a.k0 = 0; a.zblk = K; a.R = R;
     const int tiles = (F - 1 + 63) / 64;
-    unsigned nblk = (unsigned)((long long)R * K * (tiles + 1) * chunks);
-    const unsigned nblk_lds = DISCO_COV_XCD ? (nblk + 7) / 8 * 8 : nblk;
+    const unsigned nblk = (unsigned)disco_host::xcd_grid((long long)R * K * (tiles + 1) * chunks);
+    (void)variant;
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     auto launch = [&]() {
-        if (variant == 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_split<KB_M, KB_KR, true>), dim3(nblk), dim3(64 * cov_split_waves<KB_KR, true>()), 0, 0, a);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_split_lds<KB_M, KB_KR, true>), dim3(nblk_lds), dim3(64 * cov_split_waves<KB_KR, true>()), 0, 0, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_split_lds<KB_M, KB_KR, true>), dim3(nblk), dim3(64 * cov_split_waves<KB_KR, true>()), 0, 0, a);
     };
     launch();
     hipDeviceSynchronize();

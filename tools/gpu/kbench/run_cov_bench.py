@@ -20,7 +20,7 @@ for so in sorted(glob.glob(os.path.join(here, os.environ.get('KB_GLOB', 'cov_ben
     lib = ctypes.CDLL(so)
     lib.cov_bench.restype = ctypes.c_float
     lib.cov_bench.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6
-    for variant in ((0, 1) if so.endswith('_base.so') else (1,)):
+    for variant in (1,):
         for chunks in (1, 2):
             part = torch.zeros((R * K, chunks, F, NP, 4), device=dev)
             ms = lib.cov_bench(variant, X.data_ptr(), mask.data_ptr(), Z.data_ptr(), part.data_ptr(), R, K, T, F, chunks, 5)
