@@ -10,12 +10,11 @@ namespace disco_host {
 template <int P>
 static void launch(const SolveSrc& src, long long n_prob, double mu, c32* w, c32* t1, hipStream_t s) {
     const long long grid = (n_prob + DppSolveGeom<P>::PROBS - 1) / DppSolveGeom<P>::PROBS;
-    if (src.part)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gevd_mwf_r1_dpp<P, true>), dim3((unsigned)grid), dim3(DppSolveGeom<P>::THREADS), 0, s, src, n_prob, mu,
-                           w, t1);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gevd_mwf_r1_dpp<P, false>), dim3((unsigned)grid), dim3(DppSolveGeom<P>::THREADS), 0, s, src, n_prob, mu,
-                           w, t1);
+    with_bool(src.part != nullptr, [&](auto part) {
+        constexpr bool FROM_PART = decltype(part)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gevd_mwf_r1_dpp<P, FROM_PART>), dim3((unsigned)grid), dim3(DppSolveGeom<P>::THREADS), 0, s, src, n_prob,
+                           mu, w, t1);
+    });
 }
 
 void launch_solve_dpp(int P, const SolveSrc& src, long long n_prob, double mu, c32* w, c32* t1, hipStream_t s) {

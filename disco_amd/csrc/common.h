@@ -103,6 +103,15 @@ __device__ __forceinline__ float quad_xor_add(float x) {
 #endif
 }
 
+// Butterfly sum over a group of G lanes (G = 64: the wave); every lane of the group ends with the result.  The order of the additions
+// is part of the result: a site that adds in another order, or reduces two values in one interleaved loop, keeps its own loop.
+template <int G>
+__device__ __forceinline__ double group_sum(double x) {
+#pragma unroll
+    for (int off = G / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off, G);
+    return x;
+}
+
 // LDS exchange fences.  The exchange buffers are WAVE-PRIVATE, so no s_barrier is needed: a wave's DS
 // instructions execute in issue order, and all that has to be prevented is (a) the compiler moving a read
 // above the writes it depends on through another lane, (b) a read issuing before this wave's own writes have

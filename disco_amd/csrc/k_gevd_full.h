@@ -64,8 +64,7 @@ __device__ __forceinline__ void jacobi_apply(c64& x, c64& y, double c, double s,
 
 // f_i of a kept pair, 0 for a dropped one (pos: the pair's position in the descending order)
 __device__ __forceinline__ double gevd_kept_gain(double d, int pos, int r, double mu) {
-    const double dc = fmin(fmax(d, SOLVE_EPS), SOLVE_ETA);
-    return pos < r ? dc / (dc + mu) : 0.0;
+    return pos < r ? mwf_gain(d, mu) : 0.0;
 }
 
 // ---- P <= 4: one thread per pencil ---------------------------------------------------------------------------------------------------
@@ -215,9 +214,7 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(SolveGeom<P>::THREADS, SolveGeom
     c64(*Rot)[2] = s_rot[slot];
 
     c32 rowA[P], rowB[P];
-    SolveSrc src = {};
-    src.Rss = Rxx;
-    src.Rnn = Rnn;
+    const SolveSrc src = SolveSrc::matrices(Rxx, Rnn);
     if (col) {
         solve_load_row<P, false>(src, pid, j, rowA, rowB);
     } else {

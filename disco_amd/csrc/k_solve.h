@@ -8,6 +8,8 @@
 //     t1 = L^-H v0 * L[0,0] * conj(v0[0]),     w = t1 * d0 / (d0 + mu),   d0 clamped to [eps, 1e6]
 // (oracle/mwf_oracle.py:gevd_mwf_r1_hermitian; checked against the reference's own outputs).
 //
+// (The one description of the algorithm and the one statement of its rules, DISCO_TRACE_OK ... mwf_gain below: k_solve_small.h,
+// k_solve_dpp.h and k_solve_wide.h describe their layouts only.)
 // (9 <= P <= 16 of the batch solve run on the register / DPP form of the same algorithm by default: k_solve_dpp.h; this file is the
 // LDS form -- P = 5 ... 8, the online kernel, k_mwf_variants, and option "solve_dpp" = 0.)
 // Mapping: a group of G = 4 / 8 / 16 lanes owns one problem, lane j owns column j.  Everything is float64:
@@ -81,6 +83,31 @@ __device__ __forceinline__ double rcp64(double x) {
     return y;
 }
 
+// ---- the decisions of the solve, stated ONCE for its four forms (this file, k_solve_small.h, k_solve_dpp.h, k_solve_wide.h) ----------
+// Statement macros on the solver's own locals, not functions: hipcc simplifies a function on its own before it inlines it, and a compare
+// the solver shares with a rule (tr > 0, |tau|^2 > 0, the repeated 1 - tau test) is then merged later and in another shape -- every
+// function form tried changed the device code of all four solvers (CHANGES.md).  Expanded they are the text each solver carried before.
+// ok: false for NaN / inf / the zero matrix (Rxx = 0), the squarings then start `done`; tr_bad: finite, non-zero (fro2 = ||M||_F^2), tr <= 0
+#define DISCO_TRACE_OK(tr) ((tr) > 0.0 && (tr) < 1.7e308)
+#define DISCO_TRACE_BAD(tr, fro2) (!((tr) > 0.0) && (fro2) > 0.0 && (fro2) < 1.7e308)
+// after square number `it`: tau_re = Re tr(B^2), normalisable = tr(B^2) != 0; exit0 remembers a stop at the first check.  _F32: the
+// packed-float32 squarings of the online mode compare in float (and flag nothing: their pencils are PSD by construction).
+#define DISCO_SQUARING_AFTER(it, tau_re, normalisable, done, exit0)                     \
+    do {                                                                                \
+        if ((it) == 0) exit0 = !done && (1.0 - (tau_re) < DISCO_SQUARING_DONE);         \
+        done = done || (1.0 - (tau_re) < DISCO_SQUARING_DONE) || !(normalisable);       \
+    } while (0)
+#define DISCO_SQUARING_AFTER_F32(tau, done) done = done || (1.0f - (tau) < (float)DISCO_SQUARING_DONE) || !((tau) > 0.f)
+// kept = tr(B^2) of the square that was kept.  The caller adds the third case, a negative Rayleigh quotient.
+#define DISCO_SUSPECT(P, tr_bad, exit0, kept) ((P) > 1 && ((tr_bad) || ((exit0) && (kept) < DISCO_KEPT_TAU_MIN)))
+
+// the eigenvalue clamped to [eps, 1e6] (internal_formulas.py:59-60), and the gain d / (d + mu) of the clamped eigenvalue
+__device__ __forceinline__ double clamp_eigenvalue(double d0) { return fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA); }
+__device__ __forceinline__ double mwf_gain(double d0, double mu) {
+    const double dcl = clamp_eigenvalue(d0);
+    return dcl / (dcl + mu);
+}
+
 template <int P>
 struct SolveGeom {
     static constexpr int G = P <= 4 ? 4 : (P <= 8 ? 8 : 16);
@@ -111,6 +138,23 @@ struct SolveSrc {
     // k_step2_cov_fused<SKIPLOC>): entries (j, c) with max(j, c) < M_loc come from here.  M_loc = 0: unused.
     const float4* part_loc;
     int chunks_loc, M_loc;
+
+    // the two ways a source is made: full matrices, or the partial sums a covariance call left pending (PendingSums, host.h).  Those go
+    // to the solvers UNSCALED (inv_T = 1): w and t1 do not change when Rxx and Rnn are scaled together, and an entry that arrives as one
+    // float32 block or as the (hi, lo) pair of a float64 total then reaches the float64 arithmetic exactly as it was summed (k_solve_dpp.h)
+    __host__ __device__ static SolveSrc matrices(const c32* Rss, const c32* Rnn) {
+        SolveSrc s = {};
+        s.Rss = Rss, s.Rnn = Rnn;
+        s.F = s.chunks = 1, s.inv_T = 1.f;
+        return s;
+    }
+    template <class Pending>
+    static SolveSrc pending(const Pending& ps, int F) {
+        SolveSrc s = {};
+        s.part = ps.part, s.F = F, s.chunks = ps.blocks, s.inv_T = 1.f;
+        s.part_loc = ps.part_loc, s.chunks_loc = ps.blocks_loc, s.M_loc = ps.M_loc;
+        return s;
+    }
 };
 
 // row j of both Hermitian matrices of problem pid: rs[c] = Rss[j][c], rn[c] = Rnn[j][c]
@@ -267,12 +311,12 @@ __device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::Y
             if (i == j) trl = g[i].x;
 #pragma unroll
         for (int off = G / 2; off >= 1; off >>= 1) trl += __shfl_xor(trl, off, G);
-        const bool ok = trl > 0.0 && trl < 1.7e308;            // false for NaN / inf / the zero matrix (Rxx = 0)
+        const bool ok = DISCO_TRACE_OK(trl);
         const double rt = ok ? rcp64(trl) : 0.0;
 #pragma unroll
         for (int i = 0; i < P; ++i) g[i] = ok ? zscale(g[i], rt) : make_double2(0.0, 0.0);
         done = !ok;
-        tr_bad = !(trl > 0.0) && fro > 0.0 && fro < 1.7e308;
+        tr_bad = DISCO_TRACE_BAD(trl, fro);
     }
     for (int it = 0; it < DISCO_SQUARINGS_MAX; ++it) {
         DISCO_GROUP_SYNC();                                    // previous readers of Ym (Y above / the last square) are done
@@ -317,8 +361,7 @@ __device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::Y
 #pragma unroll
             for (int i = 0; i < P; ++i) g[i] = zmul(nn[i], itau);
         }
-        if (it == 0) exit0 = !done && (1.0 - tc.x < DISCO_SQUARING_DONE);
-        done = done || (1.0 - tc.x < DISCO_SQUARING_DONE) || !(den > 0.0);
+        DISCO_SQUARING_AFTER(it, tc.x, den > 0.0, done, exit0);
         if (!__any(!done)) break;                              // wave-uniform exit: finished groups keep squaring a projector
     }
 
@@ -346,7 +389,7 @@ __device__ __forceinline__ bool group_dominant(c64* g, c64 (*Ym)[SolveGeom<P>::Y
 #pragma unroll
         for (int off = G / 2; off >= 1; off >>= 1) kept += __shfl_xor(kept, off, G);
         DISCO_CONSUME(kept);
-        *suspect = P > 1 && (tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN));
+        *suspect = DISCO_SUSPECT(P, tr_bad, exit0, kept);
     }
     const bool have = best > 0.0;                          // false: C = 0 or not finite -> v0 = e0 (d0 is clamped below)
     const double rb = have ? rsqrt64(best) : 0.0;
@@ -499,9 +542,8 @@ __device__ __forceinline__ bool gevd_pass_group(const c32* rowA, const c64* Lm, 
         for (int off = G / 2; off >= 1; off >>= 1) e += __shfl_xor(e, off, G);
         d0 = have ? e : 0.0;
     }
-    const double dcl = fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA);
+    const double gain = mwf_gain(d0, mu);
     const c64 gsc = make_double2(l00 * v0[0].x, -l00 * v0[0].y);     // L[0,0] conj(v0[0]) = (Q^-1)[0,0]
-    const double gain = dcl / (dcl + mu);
     t1_j = make_double2(0.0, 0.0);
 #pragma unroll
     for (int i = 0; i < P; ++i) {

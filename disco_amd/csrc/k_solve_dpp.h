@@ -1,6 +1,5 @@
 // Rank-1 GEVD-MWF solve for 9 <= P <= 16 with the matrices in REGISTERS and every "entry of another lane's column" read through
-// DPP row_newbcast (dpp64.h) instead of LDS -- same algorithm, same formulas and the same breakdown rules as gevd_solve_group
-// (k_solve.h; intern_filter(..., type='gevd', rank=1), disco_theque/se_utils/internal_formulas.py:56-73).
+// DPP row_newbcast (dpp64.h) instead of LDS -- the algorithm and its rules are those of k_solve.h (described at its top).
 //
 // Why: the LDS form of the P = 15 solve (C5: 820 800 pencils per launch) spent 7.2 ms per launch with 2 039 M VALU and 392 M LDS
 // instructions -- one broadcast ds_read_b128 per complex multiply-add, i.e. ~5 ms of LDS time at 128 B/clk/CU against ~1.9 ms of
@@ -270,12 +269,12 @@ __device__ __forceinline__ bool gevd_pass_dpp(const SolveSrc& src, const long lo
         for (int i = 0; i < P; ++i)
             if (i == j) dj = g[i].x;
         const double trl = BcReal(dj).sum();
-        const bool ok = trl > 0.0 && trl < 1.7e308;            // false for NaN / inf / the zero matrix (Rxx = 0)
+        const bool ok = DISCO_TRACE_OK(trl);
         const double rt = ok ? rcp64(trl) : 0.0;
 #pragma unroll
         for (int i = 0; i < P; ++i) g[i] = zsel(ok, zscale(g[i], rt), make_double2(0.0, 0.0));
         done = !ok;
-        tr_bad = !(trl > 0.0) && fro > 0.0 && fro < 1.7e308;
+        tr_bad = DISCO_TRACE_BAD(trl, fro);
     }
     for (int it = 0; it < DISCO_SQUARINGS_MAX; ++it) {
         DISCO_DPP_SETTLE();
@@ -301,8 +300,7 @@ __device__ __forceinline__ bool gevd_pass_dpp(const SolveSrc& src, const long lo
 #pragma unroll
             for (int i = 0; i < P; ++i) g[i] = zmul(nn[i], itau);
         }
-        if (it == 0) exit0 = !done && (1.0 - tc.x < DISCO_SQUARING_DONE);
-        done = done || (1.0 - tc.x < DISCO_SQUARING_DONE) || !(den > 0.0);
+        DISCO_SQUARING_AFTER(it, tc.x, den > 0.0, done, exit0);
         if (!__any(!done)) break;
     }
     DISCO_DPP_SETTLE();
@@ -317,7 +315,7 @@ __device__ __forceinline__ bool gevd_pass_dpp(const SolveSrc& src, const long lo
         const BcReal nv(nrm);
         double kept = nv.sum();                        // tr(B^2) of the kept square (summed by every lane: DPP under a uniform EXEC)
         DISCO_CONSUME(kept);
-        suspect = tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN);
+        suspect = DISCO_SUSPECT(P, tr_bad, exit0, kept);
         double best = nv.template get<0>();
         int bj = 0;
         static_for<1, P>([&](auto K) {
@@ -385,9 +383,8 @@ __device__ __forceinline__ bool gevd_pass_dpp(const SolveSrc& src, const long lo
         d0 = have ? es : 0.0;
     }
     const c64 v00 = BcVec(v).template get<0>();
-    const double dcl = fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA);
     const c64 gsc = make_double2(l00 * v00.x, -l00 * v00.y);   // L[0,0] conj(v0[0]) = (Q^-1)[0,0]
-    gain_out = dcl / (dcl + mu);
+    gain_out = mwf_gain(d0, mu);
     t1_out = zmul(q, gsc);
     return suspect || d0 < 0.0;                               // the dominant eigenvalue is negative: not the top one
 }

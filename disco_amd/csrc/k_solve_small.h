@@ -1,6 +1,6 @@
 // Rank-1 GEVD-MWF for SMALL pencils (P <= 4: every step-1 solve of a node with up to 4 microphones), one THREAD per
-// problem.  Same algorithm and the same float64 arithmetic as k_solve.h (Cholesky whitening, dominant eigenpair by
-// repeated squaring, back substitution; internal_formulas.py:56-73) -- but at this size a group of 4 lanes spends more
+// problem.  The algorithm, its float64 arithmetic and its rules are those of k_solve.h (described at its top) -- but at this size a
+// group of 4 lanes spends more
 // instructions on hand-offs (LDS round trips, fences, shuffle reductions) than on arithmetic, so everything lives in the
 // registers of one thread: no LDS or shuffles in the arithmetic (only the wave-cooperative fetch of the partial sums goes
 // through LDS), 64 problems per wave instead of 16.  The Hermitian matrices are held as (real diagonal, strict lower
@@ -221,9 +221,9 @@ __device__ __forceinline__ bool gevd_solve_thread_pass(LA load_a, LB load_b, con
         for (int i = 0; i < P; ++i) B.d[i] = shift ? B.d[i] + sh : B.d[i];
         tr = shift ? tr + P * sh : tr;
     }
-    const bool tr_bad = !(tr > 0.0) && fro > 0.0 && fro < 1.7e308;
+    const bool tr_bad = DISCO_TRACE_BAD(tr, fro);
     bool exit0 = false;
-    const bool ok = tr > 0.0 && tr < 1.7e308;
+    const bool ok = DISCO_TRACE_OK(tr);
     {
         const double rt = ok ? rcp64(tr) : 0.0;
 #pragma unroll
@@ -257,7 +257,7 @@ __device__ __forceinline__ bool gevd_solve_thread_pass(LA load_a, LB load_b, con
 #pragma unroll
                 for (int q = 0; q < NO; ++q) Bf.o[q] = scale_by_half<0>(S.o[q], rr);
             }
-            done = done || (1.0f - tau < (float)DISCO_SQUARING_DONE) || !(tau > 0.f);
+            DISCO_SQUARING_AFTER_F32(tau, done);
         }
         // the longest column of the kept square and STEPS32 power steps, still in float32 (B comes back to float64 only afterwards: the
         // two copies never live together)
@@ -349,8 +349,7 @@ __device__ __forceinline__ bool gevd_solve_thread_pass(LA load_a, LB load_b, con
 #pragma unroll
             for (int q = 0; q < NO; ++q) B.o[q] = zscale(S.o[q], rtau);
         }
-        if (it == 0) exit0 = !done && (1.0 - tau < DISCO_SQUARING_DONE);
-        done = done || (1.0 - tau < DISCO_SQUARING_DONE) || !(tau > 0.0);
+        DISCO_SQUARING_AFTER(it, tau, tau > 0.0, done, exit0);
     }
     }
     // ---- B = v0 v0^H: the longest column (ties: lowest index), normalised
@@ -448,13 +447,12 @@ __device__ __forceinline__ bool gevd_solve_thread_pass(LA load_a, LB load_b, con
         d0 += q[i].x * sj.x + q[i].y * sj.y;
     }
     d0 = have ? d0 : 0.0;
-    const double dcl = fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA);
-    gain_out = dcl / (dcl + mu);
+    gain_out = mwf_gain(d0, mu);
     const c64 gsc = make_double2(Ld[0] * v0[0].x, -Ld[0] * v0[0].y);
 #pragma unroll
     for (int i = 0; i < P; ++i) t1[i] = zmul(q[i], gsc);
     // (the SQ32 form is reached only from the online mode, whose pencils are PSD by construction: it flags nothing)
-    return !SQ32 && P > 1 && (tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN) || d0 < 0.0);
+    return !SQ32 && P > 1 && (DISCO_SUSPECT(P, tr_bad, exit0, kept) || d0 < 0.0);
 }
 
 // w, t1: this problem's P filter entries.  Contains a wave-wide vote: every lane of the wave must call it (dead lanes pass Rxx = 0, Rnn = I).

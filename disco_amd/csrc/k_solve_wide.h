@@ -1,8 +1,6 @@
 // Rank-1 GEVD-MWF solve for 17 <= P <= 32 (networks whose step-2 pencil P = M + K - 1 exceeds 16 channels).
 //
-// The algorithm is the one of k_solve.h, step for step: Cholesky of Rnn with the pivot floor, whitening C = L^-1 Rxx L^-H by two
-// substitutions, the top eigenpair by repeated squaring of C / tr C with the first-stop and trace guards, DISCO_POWER_STEPS power
-// steps, q = L^-H v0, d0 = q^H Rxx q, the same w / t1 / mu semantics, and an indefinite pencil solved again shifted by ||C||_F I.
+// The algorithm is the one described at the top of k_solve.h, step for step, with the rules stated there (DISCO_TRACE_OK ... mwf_gain).
 //
 // Mapping: ONE WAVE PER PENCIL, the matrices in LDS.  A 32 x 32 complex float64 matrix is 16 KiB: a 32-lane group owning one column
 // per lane (the P <= 16 form) would need 2 x 32 complex doubles of column per lane in the squaring alone (256 VGPRs) and spill.  Here
@@ -28,12 +26,6 @@ struct SolveWideLds {
     c64 Y[SW_PMAX][SW_YW];                       // Y = L^-1 Rxx, then C (transposed), then the squares
     c64 V[SW_PMAX];                              // the eigenvector / q
 };
-
-__device__ __forceinline__ double wave_sum64(double x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
 
 // both matrices of pencil pid into LDS.  Partial sums: the chunks are combined in float64 and rounded ONCE to float32, exactly as
 // solve_load_row does (the lower triangle is the conjugate of the upper one, the diagonal is real).
@@ -145,7 +137,7 @@ __device__ __forceinline__ bool wide_pass(SolveWideLds& s, int P, int lane, doub
     double fro = 0.0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) fro = fma(g[r].x, g[r].x, fma(g[r].y, g[r].y, fro));
-    fro = wave_sum64(fro);
+    fro = group_sum<64>(fro);
     const bool own_diag = j < P && j >= r0 && j < r0 + 16;
     if (shift) {
         const double sh = sqrt(fro);
@@ -159,13 +151,13 @@ __device__ __forceinline__ bool wide_pass(SolveWideLds& s, int P, int lane, doub
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             if (own_diag && r0 + r == j) trl = g[r].x;
-        trl = wave_sum64(trl);
-        const bool ok = trl > 0.0 && trl < 1.7e308;
+        trl = group_sum<64>(trl);
+        const bool ok = DISCO_TRACE_OK(trl);
         const double rt = ok ? rcp64(trl) : 0.0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) g[r] = ok ? zscale(g[r], rt) : make_double2(0.0, 0.0);
         done = !ok;
-        tr_bad = !(trl > 0.0) && fro > 0.0 && fro < 1.7e308;
+        tr_bad = DISCO_TRACE_BAD(trl, fro);
     }
     for (int it = 0; it < DISCO_SQUARINGS_MAX; ++it) {
         DISCO_GROUP_SYNC();                      // every lane has read the previous content of Y
@@ -189,8 +181,8 @@ __device__ __forceinline__ bool wide_pass(SolveWideLds& s, int P, int lane, doub
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             if (own_diag && r0 + r == j) tc = nn[r];
-        tc.x = wave_sum64(tc.x);
-        tc.y = wave_sum64(tc.y);
+        tc.x = group_sum<64>(tc.x);
+        tc.y = group_sum<64>(tc.y);
         const double den = tc.x * tc.x + tc.y * tc.y;
         const double rden = den > 0.0 ? rcp64(den) : 0.0;
         const c64 itau = make_double2(tc.x * rden, -tc.y * rden);
@@ -198,8 +190,7 @@ __device__ __forceinline__ bool wide_pass(SolveWideLds& s, int P, int lane, doub
 #pragma unroll
             for (int r = 0; r < 16; ++r) g[r] = zmul(nn[r], itau);
         }
-        if (it == 0) exit0 = !done && (1.0 - tc.x < DISCO_SQUARING_DONE);
-        done = done || (1.0 - tc.x < DISCO_SQUARING_DONE) || !(den > 0.0);
+        DISCO_SQUARING_AFTER(it, tc.x, den > 0.0, done, exit0);
         if (done) break;                         // wave-uniform: one pencil per wave
     }
     // ---- B = v0 v0^H: the longest column (ties: lowest index)
@@ -221,7 +212,7 @@ __device__ __forceinline__ bool wide_pass(SolveWideLds& s, int P, int lane, doub
     double kept = nrm;
 #pragma unroll
     for (int off = 16; off >= 1; off >>= 1) kept += __shfl_xor(kept, off);
-    const bool suspect = P > 1 && (tr_bad || (exit0 && kept < DISCO_KEPT_TAU_MIN));
+    const bool suspect = DISCO_SUSPECT(P, tr_bad, exit0, kept);
     const bool have = best > 0.0;
     const double rb = have ? rsqrt64(best) : 0.0;
     DISCO_GROUP_SYNC();
@@ -282,12 +273,12 @@ __device__ __forceinline__ bool wide_pass(SolveWideLds& s, int P, int lane, doub
         }
         e = qj.x * sj.x + qj.y * sj.y;
     }
-    e = wave_sum64(e);
+    e = group_sum<64>(e);
     const double d0 = have ? e : 0.0;
-    const double dcl = fmin(fmax(d0, SOLVE_EPS), SOLVE_ETA);
+    const double dcl = clamp_eigenvalue(d0);
     const double l00 = s.L[sw_lt(0, 0)].y;
     const c64 gsc = make_double2(l00 * v00.x, -l00 * v00.y);     // L[0,0] conj(v0[0]) = (Q^-1)[0,0]
-    gain_out = dcl / (dcl + mu);
+    gain_out = dcl / (dcl + mu);                                 // mwf_gain, around the read of L: the listing follows the statement order
     t1_j = zmul(qj, gsc);
     return suspect || d0 < 0.0;
 }
