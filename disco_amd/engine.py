@@ -3,6 +3,9 @@
 Arrays may be given as numpy arrays (copied host->device through the library's own hipMemcpy), as `DevBuf`
 (device resident, returned by every method), or as torch ROCm tensors (zero-copy through `data_ptr()`).
 All compute happens in libdisco_hip.so; this file only marshals pointers.  No CPU fallback exists.
+The marshalling is stated once, in the helpers under "plumbing": `_out` (caller-owned or fresh output), `_alias` (a second argument that
+may be the first), `_ptr` (optional buffer -> pointer or NULL), `_span_stops` / `_span_stops_dev` (`stop` of a metric), `_chunk_plan` /
+`_chunks` (a batch walked under a workspace budget), `_pencils` (the solvers' prologue), `_selftest_pair`; each method names its dialect.
 """
 import ctypes as C
 
@@ -52,6 +55,11 @@ class DevBuf:
                 self.free()
         except Exception:
             pass
+
+
+def _ptr(buf):
+    """Device pointer of an optional output the method allocated, NULL for one not asked for."""
+    return buf.ptr if buf is not None else None
 
 
 def parse_mask_type(mask):
@@ -126,6 +134,45 @@ class Engine:
         except Exception:
             pass
 
+    # Every helper below that uploads returns the keep-alive beside the pointer, and its caller binds it to a local: a temporary DevBuf
+    # frees its memory when the last reference goes, which must not happen before the library call that got the pointer has returned.
+    def _out(self, out, shape, dtype, check):
+        """An output the caller may own -> (array to return, device pointer, keep-alive): a fresh DevBuf of `shape` for None, else `out`
+        itself after `check`: 'shape' (exactly `shape`) or 'size' (as many elements), both refusing a NumPy array, or 'any' (nothing is
+        checked; a NumPy array is then uploaded to a temporary that receives the result in its place)."""
+        if out is None:
+            out = self.empty(shape, dtype)
+        elif check == 'shape':
+            assert tuple(out.shape) == tuple(shape) and not isinstance(out, np.ndarray)
+        elif check == 'size':
+            assert int(np.prod(tuple(out.shape))) == int(np.prod(shape, dtype=np.int64)) and not isinstance(out, np.ndarray)
+        else:
+            assert check == 'any', check
+        return (out,) + self.to_device(out, dtype)
+
+    def _alias(self, b, a, dev_a, dtype, none):
+        """(pointer, keep-alive) of `b`, an argument that may be the object `a` already on the device as `dev_a`: the same object gives the
+        same pointer with one upload (the C side picks its route by comparing the two pointers).  none='same': None stands for `a` as
+        well (the whole-path masks); none='null': None reaches C as NULL."""
+        assert none in ('same', 'null'), none
+        if b is a or (b is None and none == 'same'):
+            return dev_a
+        return self.to_device(b, dtype)
+
+    def _pencils(self, A, B):
+        """The solvers' prologue: A, B (..., P, P) -> (shape, P, number of pencils, pointer of A, pointer of B, keep-alive)."""
+        shape = tuple(A.shape)
+        pa, ka = self.to_device(A, np.complex64)
+        pb, kb = self.to_device(B, np.complex64)
+        return shape, shape[-1], int(np.prod(shape[:-2], dtype=np.int64)), pa, pb, (ka, kb)
+
+    def _selftest_pair(self, fn, inputs, dtype, shape):
+        """fn(inputs (n,)..., n) -> (out_hw, out_ref), each `shape`: one instruction-level self-test of the library and its plain restatement."""
+        dev = [self.to_device(a, dtype) for a in inputs]
+        hw, ref = self.empty(shape, dtype), self.empty(shape, dtype)
+        self._chk(fn(self.ctx, *(p for p, _ in dev), inputs[0].shape[0], hw.ptr, ref.ptr, self.stream))
+        return hw, ref
+
     # ---- online / adaptive mode (SURVEY 8f-2; primitives internal_formulas.py:84-103 and :56-73)
     def online_mwf(self, X, mask, Z=None, lambda_cor=0.95, mu=None, update_every=1, init_diag=1e-3, want_w=False):
         """Exponentially smoothed covariances + a filter update every `update_every` frames, causal in t.
@@ -137,7 +184,7 @@ class Engine:
         out = self.empty((self.R, self.Kl, self.T, self.F), np.complex64)
         w = self.empty((self.R, self.Kl, self.F, P), np.complex64) if want_w else None
         self._chk(self.lib.disco_online_mwf(self.ctx, px, pz, pm, P, lambda_cor, self.cfg.mu if mu is None else mu,
-                                            update_every, init_diag, out.ptr, w.ptr if w else None, self.stream))
+                                            update_every, init_diag, out.ptr, _ptr(w), self.stream))
         return (out, w) if want_w else out
 
     def tango_online(self, y, mask_z, mask_w=None, lambda_cor=0.95, update_every=1, init_diag=1e-3, want_z=True,
@@ -145,17 +192,12 @@ class Engine:
         """The two-step path in online mode: y (R,K,M,L), masks (R,K,T,F) -> out (R,K,L)[, z_y, yf (R,K,T,F)]."""
         py, ky = self.to_device(y, np.float32)
         pmz, kmz = self.to_device(mask_z, np.float32)
-        if mask_w is None or mask_w is mask_z:
-            pmw, kmw = pmz, kmz
-        else:
-            pmw, kmw = self.to_device(mask_w, np.float32)
-        if out is None:
-            out = self.empty((self.R, self.K, self.Lsamp), np.float32)
-        po, ko = self.to_device(out, np.float32)
+        pmw, kmw = self._alias(mask_w, mask_z, (pmz, kmz), np.float32, none='same')
+        out, po, ko = self._out(out, (self.R, self.K, self.Lsamp), np.float32, 'any')
         z = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_z else None
         yf = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_yf else None
-        self._chk(self.lib.disco_tango_online(self.ctx, py, pmz, pmw, lambda_cor, update_every, init_diag, po,
-                                              z.ptr if z else None, yf.ptr if yf else None, None, 0, self.stream))
+        self._chk(self.lib.disco_tango_online(self.ctx, py, pmz, pmw, lambda_cor, update_every, init_diag, po, _ptr(z), _ptr(yf), None, 0,
+                                              self.stream))
         return out, z, yf
 
     def online_stream(self, lambda_cor=0.95, update_every=1, init_diag=1e-3):
@@ -211,9 +253,49 @@ class Engine:
             raise ValueError(f'stop must be None, a scalar or an ({n},) array, one entry per signal: got shape {stops.shape}')
         if not np.issubdtype(stops.dtype, np.integer):
             raise ValueError(f'stop must hold integers, got {stops.dtype}')
+        return None, self._upload_stops(stops, L, start, stop)
+
+    def _upload_stops(self, stops, L, start, given):
+        """The range check and the upload of an (n,) integer array of stops -> (device pointer, keep-alive); `given` is what the error shows."""
         if int(start) < 0 or np.any(stops < start) or np.any(stops > L):
-            raise ValueError(f'need 0 <= start <= stop <= L = {L}: start {start}, stop {stop}')
-        return None, self.to_device(np.ascontiguousarray(stops, dtype=np.int32), np.int32)
+            raise ValueError(f'need 0 <= start <= stop <= L = {L}: start {start}, stop {given}')
+        return self.to_device(np.ascontiguousarray(stops, dtype=np.int32), np.int32)
+
+    def _span_stops_dev(self, stop, n, L, start, dialect):
+        """`stop` of an entry point that takes one stop per signal or NULL -> (device pointer, keep-alive), or (None, None) for None, when
+        `start` alone is checked.  dialect 'each' (bss_estimates): a scalar is repeated n times, an array goes through `_span_stops`;
+        'broadcast' (stoi): whatever np.broadcast_to takes to (n,), converted to int64 first, so a float is truncated, not refused."""
+        if stop is None:
+            if not 0 <= int(start) <= L:
+                raise ValueError(f'need 0 <= start <= L = {L}: start {start}')
+            return None, None
+        if dialect == 'broadcast':
+            return self._upload_stops(np.broadcast_to(np.asarray(stop, dtype=np.int64), (n,)), L, start, stop)
+        assert dialect == 'each', dialect
+        return self._span_stops(stop if np.ndim(stop) else np.full((n,), int(stop), dtype=np.int64), n, L, start)[1]
+
+    def _chunk_plan(self, n, ws_bytes, budget_bytes, default_budget, probe, name):
+        """A batch of n items walked under a workspace budget -> (items per chunk, workspace DevBuf): ws_bytes(k) is the library's size for
+        k items, at least one item goes per chunk.  ws_bytes(1) == 0 means a shape outside the supported range: `probe()` calls the
+        entry point with NULLs so that the library names the limit (nothing is launched), then DiscoError."""
+        per_item = int(ws_bytes(1))
+        if per_item == 0:
+            self._chk(probe())
+            raise DiscoError(f'{name}: unsupported shape')
+        budget = default_budget if budget_bytes is None else int(budget_bytes)
+        step = max(1, min(n, budget // per_item))
+        return step, self.empty((int(ws_bytes(step)) // 8 + 1,), np.float64)
+
+    def _chunks(self, n, step, *inputs):
+        """The walk itself: yields (i0, n_chunk, pointer...) with one float32 pointer per (array, elements per item) in `inputs`.  A NumPy
+        array is sliced and uploaded chunk by chunk (the upload stays referenced until the next chunk is asked for); a device-resident
+        one is read in place, its pointer stepped."""
+        host = [isinstance(a, np.ndarray) for a, _ in inputs]
+        base = [None if h else self.to_device(a, np.float32) for (a, _), h in zip(inputs, host)]
+        for i0 in range(0, n, step):
+            m = min(step, n - i0)
+            dev = [self.to_device(a[i0:i0 + m], np.float32) if h else (b[0] + 4 * i0 * per, b[1]) for (a, per), h, b in zip(inputs, host, base)]
+            yield (i0, m) + tuple(p for p, _ in dev)
 
     def pair_stats(self, a, b, start=0, stop=None):
         """a, b (n_sig, L) float32 -> (n_sig, 8) float64 moments of a[:, start:stop], b[:, start:stop]
@@ -222,7 +304,7 @@ class Engine:
         n_sig, L = a.shape
         stop, dstop = self._span_stops(stop, n_sig, L, start)
         pa, ka = self.to_device(a, np.float32)
-        pb, kb = (pa, ka) if b is a else self.to_device(b, np.float32)
+        pb, kb = self._alias(b, a, (pa, ka), np.float32, none='null')
         st = self.empty((n_sig, 8), np.float64)
         if dstop is not None:
             self._chk(self.lib.disco_pair_stats_spans(self.ctx, pa, pb, n_sig, L, start, dstop[0], st.ptr, self.stream))
@@ -265,7 +347,7 @@ class Engine:
         stop, dstop = self._span_stops(stop, n_pair, L, start)
         nlag = int(lag_hi) - int(lag_lo) + 1
         pa, ka = self.to_device(a, np.float32)
-        pb, kb = (pa, ka) if b is a else self.to_device(b, np.float32)
+        pb, kb = self._alias(b, a, (pa, ka), np.float32, none='null')
         wsb = int(self.lib.disco_lag_corr_workspace_bytes(self.ctx, n_pair, L, max(nlag, 1)))
         ws = self.empty((max(wsb, 8) // 8,), np.float64)
         out = self.empty((n_pair, max(nlag, 1)), np.float64)
@@ -296,34 +378,14 @@ class Engine:
             raise ValueError(f'empty batch: refs {rs}, ests {es}')
         stop, dstop = self._span_stops(stop, n_set, L, start)
         flen = int(flen)
-        per_set = int(self.lib.disco_bss_workspace_bytes(self.ctx, 1, nsrc, flen, L))
-        if per_set == 0:                                  # outside the supported range: the library names the limit, nothing is launched
-            self._chk(self.lib.disco_bss_eval(self.ctx, None, None, n_set, nsrc, n_est, L, start, L if stop is None else stop, flen, int(all_pairs),
-                                              None, None, None, 0, self.stream))
-            raise DiscoError('disco_bss_eval: unsupported shape')
-        budget = self.BSS_WORKSPACE_BUDGET if budget_bytes is None else int(budget_bytes)
-        step = max(1, min(n_set, budget // per_set))
-        wsb = int(self.lib.disco_bss_workspace_bytes(self.ctx, step, nsrc, flen, L))
-        ws = self.empty((wsb // 8 + 1,), np.float64)
+        step, ws = self._chunk_plan(
+            n_set, lambda k: self.lib.disco_bss_workspace_bytes(self.ctx, k, nsrc, flen, L), budget_bytes, self.BSS_WORKSPACE_BUDGET,
+            lambda: self.lib.disco_bss_eval(self.ctx, None, None, n_set, nsrc, n_est, L, start, L if stop is None else stop, flen, int(all_pairs),
+                                            None, None, None, 0, self.stream), 'disco_bss_eval')
         oshape = (nsrc, nsrc, 4) if all_pairs else (nsrc, 4)
         energies = np.empty((n_set, n_est) + oshape, np.float64)
         status = np.empty((n_set,), np.int32)
-        host = isinstance(refs, np.ndarray), isinstance(ests, np.ndarray)
-        pr0 = pe0 = None
-        if not host[0]:
-            pr0, kr = self.to_device(refs, np.float32)
-        if not host[1]:
-            pe0, ke = self.to_device(ests, np.float32)
-        for i0 in range(0, n_set, step):
-            n = min(step, n_set - i0)
-            if host[0]:
-                pr, kr_ = self.to_device(refs[i0:i0 + n], np.float32)
-            else:
-                pr = pr0 + 4 * i0 * nsrc * L
-            if host[1]:
-                pe, ke_ = self.to_device(ests[i0:i0 + n], np.float32)
-            else:
-                pe = pe0 + 4 * i0 * n_est * nsrc * L
+        for i0, n, pr, pe in self._chunks(n_set, step, (refs, nsrc * L), (ests, n_est * nsrc * L)):
             out = self.empty((n, n_est) + oshape, np.float64)
             st = self.empty((n,), np.int32)
             if dstop is not None:
@@ -347,20 +409,12 @@ class Engine:
         n_sig, L = shp
         if min(n_sig, L) < 1:
             raise ValueError(f'empty batch: {shp}')
-        if stop is not None and not np.ndim(stop):
-            stop = np.full((n_sig,), int(stop), dtype=np.int64)
-        stop, dstop = self._span_stops(stop, n_sig, L, start)
-        if dstop is None and not 0 <= int(start) <= L:
-            raise ValueError(f'need 0 <= start <= L = {L}: start {start}')
+        pstop, kstop = self._span_stops_dev(stop, n_sig, L, start, 'each')
         py, ky = self.to_device(y, np.float32)
         ps, ks = self.to_device(sh, np.float32)
         pz, kz = self.to_device(szh, np.float32)
-        if out is None:
-            out = self.empty((n_sig, 3, 2, L), np.float32)
-        else:
-            assert int(np.prod(tuple(out.shape))) == n_sig * 6 * L and not isinstance(out, np.ndarray)
-        po, ko = self.to_device(out, np.float32)
-        self._chk(self.lib.disco_bss_estimates(self.ctx, py, ps, pz, n_sig, L, int(start), None if dstop is None else dstop[0], po, self.stream))
+        out, po, ko = self._out(out, (n_sig, 3, 2, L), np.float32, 'size')
+        self._chk(self.lib.disco_bss_estimates(self.ctx, py, ps, pz, n_sig, L, int(start), pstop, po, self.stream))
         return out
 
     STOI_WORKSPACE_BUDGET = 1 << 30     # bytes of workspace one disco_stoi call of Engine.stoi may take
@@ -381,14 +435,7 @@ class Engine:
             raise ValueError(f'empty batch: {xs}')
         p, q, taps = stoi_resample_taps(fs_sig)
         start = int(start)
-        pstop = None
-        if stop is not None:
-            stops = np.ascontiguousarray(np.broadcast_to(np.asarray(stop, dtype=np.int64), (n_pair,)))
-            if start < 0 or np.any(stops < start) or np.any(stops > L):
-                raise ValueError(f'need 0 <= start <= stop <= L = {L}: start {start}, stop {stop}')
-            pstop, kstop = self.to_device(stops.astype(np.int32), np.int32)
-        elif not 0 <= start <= L:
-            raise ValueError(f'need 0 <= start <= L = {L}: start {start}')
+        pstop, kstop = self._span_stops_dev(stop, n_pair, L, start, 'broadcast')
         ptaps = None
         if p != q:
             if not hasattr(self, '_stoi_taps'):
@@ -397,33 +444,14 @@ class Engine:
                 self._stoi_taps[p, q] = self.to_device(taps, np.float64)
             ptaps = self._stoi_taps[p, q][0]
         n_taps = len(taps)
-        per_pair = int(self.lib.disco_stoi_workspace_bytes(self.ctx, 1, L, p, q, n_taps))
-        if per_pair == 0:                                 # outside the supported range: the library names the limit, nothing is launched
-            self._chk(self.lib.disco_stoi(self.ctx, None, None, n_pair, L, start, None, p, q, None, n_taps, None, None, None, 0, self.stream))
-            raise DiscoError('disco_stoi: unsupported shape')
-        budget = self.STOI_WORKSPACE_BUDGET if budget_bytes is None else int(budget_bytes)
-        step = max(1, min(n_pair, budget // per_pair))
-        wsb = int(self.lib.disco_stoi_workspace_bytes(self.ctx, step, L, p, q, n_taps))
-        ws = self.empty((wsb // 8 + 1,), np.float64)
+        step, ws = self._chunk_plan(
+            n_pair, lambda k: self.lib.disco_stoi_workspace_bytes(self.ctx, k, L, p, q, n_taps), budget_bytes, self.STOI_WORKSPACE_BUDGET,
+            lambda: self.lib.disco_stoi(self.ctx, None, None, n_pair, L, start, None, p, q, None, n_taps, None, None, None, 0, self.stream),
+            'disco_stoi')
         d = np.empty((n_pair,), np.float64)
         kept = np.empty((n_pair,), np.int64)
         status = np.empty((n_pair,), np.int32)
-        host = isinstance(x, np.ndarray), isinstance(y, np.ndarray)
-        px0 = py0 = None
-        if not host[0]:
-            px0, kx = self.to_device(x, np.float32)
-        if not host[1]:
-            py0, ky = self.to_device(y, np.float32)
-        for i0 in range(0, n_pair, step):
-            n = min(step, n_pair - i0)
-            if host[0]:
-                px, kx_ = self.to_device(x[i0:i0 + n], np.float32)
-            else:
-                px = px0 + 4 * i0 * L
-            if host[1]:
-                py, ky_ = self.to_device(y[i0:i0 + n], np.float32)
-            else:
-                py = py0 + 4 * i0 * L
+        for i0, n, px, py in self._chunks(n_pair, step, (x, L), (y, L)):
             out = self.empty((n, 2), np.float64)
             st = self.empty((n,), np.int32)
             self._chk(self.lib.disco_stoi(self.ctx, px, py, n, L, start, None if pstop is None else pstop + 4 * i0, p, q, ptaps, n_taps, out.ptr,
@@ -437,32 +465,17 @@ class Engine:
     def selftest_pk(self, a, b, c):
         """a, b, c (n,) complex64 -> (out_hw, out_ref), each (n, 23) complex64: the packed complex operations of
         csrc/pk.h through the v_pk_* instruction forms and through their C++ statement (include/disco_hip.h)."""
-        n = a.shape[0]
-        pa, ka = self.to_device(a, np.complex64)
-        pb, kb = self.to_device(b, np.complex64)
-        pc, kc = self.to_device(c, np.complex64)
-        hw, ref = self.empty((n, 23), np.complex64), self.empty((n, 23), np.complex64)
-        self._chk(self.lib.disco_selftest_pk(self.ctx, pa, pb, pc, n, hw.ptr, ref.ptr, self.stream))
-        return hw, ref
+        return self._selftest_pair(self.lib.disco_selftest_pk, (a, b, c), np.complex64, (a.shape[0], 23))
 
     def selftest_dpp(self, a, b):
         """a, b (n,) complex128, n a multiple of 64 -> (out_hw, out_ref), each (n, 8) complex128: the float64 DPP row-broadcast forms of
         csrc/dpp64.h through their instructions and through __shfl + plain statements (include/disco_hip.h)."""
-        n = a.shape[0]
-        pa, ka = self.to_device(a, np.complex128)
-        pb, kb = self.to_device(b, np.complex128)
-        hw, ref = self.empty((n, 8), np.complex128), self.empty((n, 8), np.complex128)
-        self._chk(self.lib.disco_selftest_dpp(self.ctx, pa, pb, n, hw.ptr, ref.ptr, self.stream))
-        return hw, ref
+        return self._selftest_pair(self.lib.disco_selftest_dpp, (a, b), np.complex128, (a.shape[0], 8))
 
     def selftest_room(self, src):
         """src (n,) float32, n a multiple of 256 -> (out_hw, out_ref), each (n // 4, 6) float32: the LDS-DMA loads and permlane swaps of
         csrc/k_room.h through their instructions and through plain statements (include/disco_hip.h)."""
-        n = src.shape[0]
-        ps, ks = self.to_device(src, np.float32)
-        hw, ref = self.empty((n // 4, 6), np.float32), self.empty((n // 4, 6), np.float32)
-        self._chk(self.lib.disco_selftest_room(self.ctx, ps, n, hw.ptr, ref.ptr, self.stream))
-        return hw, ref
+        return self._selftest_pair(self.lib.disco_selftest_room, (src,), np.float32, (src.shape[0] // 4, 6))
 
     STAGED_ROUTES = {1: 'room', 2: 'split_skiploc', 3: 'whole'}
 
@@ -473,9 +486,7 @@ class Engine:
         px, kx = self.to_device(X, np.complex64)
         pm, km = self.to_device(mask, np.float32)
         pw, kw = self.to_device(w_loc, np.complex64)
-        if z is None:
-            z = self.empty((self.R, self.K, self.T, self.F), np.complex64)
-        pz, kz = self.to_device(z, np.complex64)
+        z, pz, kz = self._out(z, (self.R, self.K, self.T, self.F), np.complex64, 'any')
         route = C.c_int(0)
         self._chk(self.lib.disco_selftest_staged_step2(self.ctx, px, pm, pw, pz, int(bool(store_z)), C.addressof(route), self.stream))
         return z, self.STAGED_ROUTES[int(route.value)]
@@ -636,11 +647,7 @@ class Engine:
         n_sig, chans, Ls = x.shape
         assert Ls == self.Lsamp
         px, kx = self.to_device(x, np.float32)
-        if out is None:
-            X = self.empty((n_sig, self.T, self.F, chans), np.complex64)
-            self._chk(self.lib.disco_stft(self.ctx, px, n_sig, chans, X.ptr, self.stream))
-            return X
-        po, ko = self.to_device(out, np.complex64)
+        out, po, ko = self._out(out, (n_sig, self.T, self.F, chans), np.complex64, 'any')
         self._chk(self.lib.disco_stft(self.ctx, px, n_sig, chans, po, self.stream))
         return out
 
@@ -650,11 +657,7 @@ class Engine:
         n_sig = Z.shape[0]
         assert tuple(Z.shape[1:]) == (self.T, self.F)
         pz, kz = self.to_device(Z, np.complex64)
-        if out is None:
-            out = self.empty((n_sig, self.Lsamp), np.float32)
-        else:
-            assert int(np.prod(tuple(out.shape))) == n_sig * self.Lsamp and not isinstance(out, np.ndarray)
-        po, ko = self.to_device(out, np.float32)
+        out, po, ko = self._out(out, (n_sig, self.Lsamp), np.float32, 'size')
         self._chk(self.lib.disco_istft(self.ctx, pz, n_sig, po, self.stream))
         return out
 
@@ -682,53 +685,34 @@ class Engine:
         px, kx = self.to_device(X, np.complex64)
         pm, km = self.to_device(mask, np.float32)
         pzs, kzs = self.to_device(Zs, np.complex64)
-        if Zn is Zs:
-            pzn, kzn = pzs, kzs
-        else:
-            pzn, kzn = self.to_device(Zn, np.complex64)
-        if not Rss_out:          # leave the partial sums in the context for gevd_mwf_r1_pending
-            self._chk(self.lib.disco_cov_masked(self.ctx, px, pm, pzs, pzn, int(bool(mask_remote)), P, None, None, self.stream))
-            return None, None
-        Rss = self.empty((self.R, self.Kl, self.F, P, P), np.complex64)
-        Rnn = self.empty((self.R, self.Kl, self.F, P, P), np.complex64)
-        self._chk(self.lib.disco_cov_masked(self.ctx, px, pm, pzs, pzn, int(bool(mask_remote)), P, Rss.ptr, Rnn.ptr,
-                                            self.stream))
+        pzn, kzn = self._alias(Zn, Zs, (pzs, kzs), np.complex64, none='null')
+        # Rss_out=False: leave the partial sums in the context for gevd_mwf_r1_pending
+        Rss = self.empty((self.R, self.Kl, self.F, P, P), np.complex64) if Rss_out else None
+        Rnn = self.empty((self.R, self.Kl, self.F, P, P), np.complex64) if Rss_out else None
+        self._chk(self.lib.disco_cov_masked(self.ctx, px, pm, pzs, pzn, int(bool(mask_remote)), P, _ptr(Rss), _ptr(Rnn), self.stream))
         return Rss, Rnn
 
     def gevd_mwf_r1(self, Rss, Rnn, mu=None, want_t1=True):
         """Rss, Rnn (..., P, P) -> w, t1 (..., P)   [intern_filter(..., 'gevd', rank=1), internal_formulas.py:56-73]"""
-        shape = tuple(Rss.shape)
-        P = shape[-1]
-        n_prob = int(np.prod(shape[:-2], dtype=np.int64))
-        pa, ka = self.to_device(Rss, np.complex64)
-        pb, kb = self.to_device(Rnn, np.complex64)
+        shape, P, n_prob, pa, pb, keep = self._pencils(Rss, Rnn)
         w = self.empty(shape[:-1], np.complex64)
         t1 = self.empty(shape[:-1], np.complex64) if want_t1 else None
-        self._chk(self.lib.disco_gevd_mwf_r1(self.ctx, pa, pb, n_prob, P, self.cfg.mu if mu is None else mu, w.ptr,
-                                             t1.ptr if want_t1 else None, self.stream))
+        self._chk(self.lib.disco_gevd_mwf_r1(self.ctx, pa, pb, n_prob, P, self.cfg.mu if mu is None else mu, w.ptr, _ptr(t1), self.stream))
         return w, t1
 
     def gevd_mwf(self, Rxx, Rnn, rank, mu=None, want_t1=True):
         """Rxx, Rnn (..., P, P) -> w, t1 (..., P)   [intern_filter(..., 'gevd', rank), internal_formulas.py:56-73, for a kept rank >= 0;
         rank >= P is full rank]"""
-        shape = tuple(Rxx.shape)
-        P = shape[-1]
-        n_prob = int(np.prod(shape[:-2], dtype=np.int64))
-        pa, ka = self.to_device(Rxx, np.complex64)
-        pb, kb = self.to_device(Rnn, np.complex64)
+        shape, P, n_prob, pa, pb, keep = self._pencils(Rxx, Rnn)
         w = self.empty(shape[:-1], np.complex64)
         t1 = self.empty(shape[:-1], np.complex64) if want_t1 else None
-        self._chk(self.lib.disco_gevd_mwf(self.ctx, pa, pb, n_prob, P, int(rank), self.cfg.mu if mu is None else mu, w.ptr,
-                                          t1.ptr if want_t1 else None, self.stream))
+        self._chk(self.lib.disco_gevd_mwf(self.ctx, pa, pb, n_prob, P, int(rank), self.cfg.mu if mu is None else mu, w.ptr, _ptr(t1),
+                                          self.stream))
         return w, t1
 
     def mwf_filter(self, Rxx, Rnn, type='r1-mwf', mu=None):
         """intern_filter's 'r1-mwf' / 'mwf' branches (internal_formulas.py:45-54, 74-76), batched: (..., P, P) -> w (..., P)."""
-        shape = tuple(Rxx.shape)
-        P = shape[-1]
-        n_prob = int(np.prod(shape[:-2], dtype=np.int64))
-        pa, ka = self.to_device(Rxx, np.complex64)
-        pb, kb = self.to_device(Rnn, np.complex64)
+        shape, P, n_prob, pa, pb, keep = self._pencils(Rxx, Rnn)
         w = self.empty(shape[:-1], np.complex64)
         self._chk(self.lib.disco_mwf_filter(self.ctx, pa, pb, n_prob, P, self.cfg.mu if mu is None else mu,
                                             {'r1-mwf': 1, 'mwf': 2}[type], w.ptr, self.stream))
@@ -737,15 +721,9 @@ class Engine:
     def gevd_mwf_r1_pending(self, P, mu=None, want_t1=False, out=None):
         """Solve straight from the partial sums the last covariance call left in the context.
         out: optional caller-owned (R, Kl, F, P) complex64 device array (DevBuf or torch tensor) for the filters."""
-        if out is None:
-            w = self.empty((self.R, self.Kl, self.F, P), np.complex64)
-        else:
-            assert tuple(out.shape) == (self.R, self.Kl, self.F, P) and not isinstance(out, np.ndarray)
-            w = out
-        pw, kw = self.to_device(w, np.complex64)
+        w, pw, kw = self._out(out, (self.R, self.Kl, self.F, P), np.complex64, 'shape')
         t1 = self.empty((self.R, self.Kl, self.F, P), np.complex64) if want_t1 else None
-        self._chk(self.lib.disco_gevd_mwf_r1_pending(self.ctx, self.cfg.mu if mu is None else mu, pw,
-                                                     t1.ptr if want_t1 else None, self.stream))
+        self._chk(self.lib.disco_gevd_mwf_r1_pending(self.ctx, self.cfg.mu if mu is None else mu, pw, _ptr(t1), self.stream))
         return w, t1
 
     def apply(self, X, w, Z=None, conj=True, out=None):
@@ -755,11 +733,7 @@ class Engine:
         px, kx = self.to_device(X, np.complex64)
         pz, kz = self.to_device(Z, np.complex64)
         pw, kw = self.to_device(w, np.complex64)
-        if out is None:
-            out = self.empty((self.R, self.Kl, self.T, self.F), np.complex64)
-        else:
-            assert tuple(out.shape) == (self.R, self.Kl, self.T, self.F) and not isinstance(out, np.ndarray)
-        po, ko = self.to_device(out, np.complex64)
+        out, po, ko = self._out(out, (self.R, self.Kl, self.T, self.F), np.complex64, 'shape')
         self._chk(self.lib.disco_apply(self.ctx, px, pz, pw, P, int(bool(conj)), po, self.stream))
         return out
 
@@ -770,12 +744,8 @@ class Engine:
         px, kx = self.to_device(X, np.complex64)
         pz, kz = self.to_device(Z, np.complex64)
         pw, kw = self.to_device(w, np.complex64)
-        if out is None:
-            out = self.empty((self.R, self.Kl, self.Lsamp), np.float32)
-        else:
-            assert int(np.prod(tuple(out.shape))) == self.R * self.Kl * self.Lsamp and not isinstance(out, np.ndarray)
-        po, ko = self.to_device(out, np.float32)
-        pyf, kyf = (None, None) if yf_out is None else self.to_device(yf_out, np.complex64)
+        out, po, ko = self._out(out, (self.R, self.Kl, self.Lsamp), np.float32, 'size')
+        pyf, kyf = self.to_device(yf_out, np.complex64)              # unchecked; None: the spectra are not stored
         rc = self.lib.disco_apply_istft_fused(self.ctx, px, pz, pw, pyf, po, self.stream)
         if rc == -2:                                              # DISCO_E_UNSUPPORTED: shape not built
             return None
@@ -787,13 +757,7 @@ class Engine:
         out: optional caller-owned device array for it."""
         P = int(w_glo.shape[-1])
         pw, kw = self.to_device(w_glo, np.complex64)
-        if out is None:
-            w_loc = self.empty((self.R, self.Kl, self.F, self.M), np.complex64)
-            po = w_loc.ptr
-        else:
-            assert tuple(out.shape) == (self.R, self.Kl, self.F, self.M) and not isinstance(out, np.ndarray)
-            w_loc = out
-            po, ko = self.to_device(out, np.complex64)
+        w_loc, po, ko = self._out(out, (self.R, self.Kl, self.F, self.M), np.complex64, 'shape')
         self._chk(self.lib.disco_filter_head(self.ctx, pw, P, po, self.stream))
         return w_loc
 
@@ -811,15 +775,10 @@ class Engine:
         py, ky = self.to_device(y, np.float32)
         pm, km = self.to_device(mask_z, np.float32)
         Kl = self.Kl
-        if X_out is None:
-            X = self.empty((self.R, Kl, self.T, self.F, self.M), np.complex64)
-            px = X.ptr
-        else:
-            X = X_out
-            px, kx = self.to_device(X_out, np.complex64)
+        X, px, kx = self._out(X_out, (self.R, Kl, self.T, self.F, self.M), np.complex64, 'any')
         Rss = self.empty((self.R, Kl, self.F, self.M, self.M), np.complex64) if want_cov else None
         Rnn = self.empty((self.R, Kl, self.F, self.M, self.M), np.complex64) if want_cov else None
-        self._chk(self.lib.disco_stft_cov_fused(self.ctx, py, pm, px, Rss.ptr if want_cov else None, Rnn.ptr if want_cov else None, self.stream))
+        self._chk(self.lib.disco_stft_cov_fused(self.ctx, py, pm, px, _ptr(Rss), _ptr(Rnn), self.stream))
         return X, Rss, Rnn
 
     def step2_cov_fused(self, X, mask_w, w_loc, want_z=True):
@@ -831,7 +790,7 @@ class Engine:
         z = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_z else None
         Rss = self.empty((self.R, self.K, self.F, P, P), np.complex64)
         Rnn = self.empty((self.R, self.K, self.F, P, P), np.complex64)
-        self._chk(self.lib.disco_step2_cov_fused(self.ctx, px, pm, pw, z.ptr if z else None, Rss.ptr, Rnn.ptr, self.stream))
+        self._chk(self.lib.disco_step2_cov_fused(self.ctx, px, pm, pw, _ptr(z), Rss.ptr, Rnn.ptr, self.stream))
         return Rss, Rnn, z
 
     def step2_cov_fused_reuse(self, X, mask_w, w_loc, want_z=False):
@@ -841,7 +800,7 @@ class Engine:
         pm, km = self.to_device(mask_w, np.float32)
         pw, kw = self.to_device(w_loc, np.complex64)
         z = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_z else None
-        self._chk(self.lib.disco_step2_cov_fused_reuse(self.ctx, px, pm, pw, z.ptr if z else None, self.stream))
+        self._chk(self.lib.disco_step2_cov_fused_reuse(self.ctx, px, pm, pw, _ptr(z), self.stream))
         return z
 
     def step2_apply_fused(self, X, w_loc, w_glo, want_z=False):
@@ -850,7 +809,7 @@ class Engine:
         pg, kg = self.to_device(w_glo, np.complex64)
         z = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_z else None
         yf = self.empty((self.R, self.K, self.T, self.F), np.complex64)
-        self._chk(self.lib.disco_step2_apply_fused(self.ctx, px, pl, pg, z.ptr if z else None, yf.ptr, self.stream))
+        self._chk(self.lib.disco_step2_apply_fused(self.ctx, px, pl, pg, _ptr(z), yf.ptr, self.stream))
         return yf, z
 
     def step2_apply_istft_fused(self, X, w_loc, w_glo):
@@ -868,10 +827,7 @@ class Engine:
         Staged kernels (z materialised), one C call (disco_tango_enhance_iterated).  Returns (out (R,K,L), yf (R,K,T,F))."""
         py, ky = self.to_device(y, np.float32)
         pmz, kmz = self.to_device(mask_z, np.float32)
-        if mask_w is None or mask_w is mask_z:
-            pmw, kmw = pmz, kmz
-        else:
-            pmw, kmw = self.to_device(mask_w, np.float32)
+        pmw, kmw = self._alias(mask_w, mask_z, (pmz, kmz), np.float32, none='same')
         out = self.empty((self.R, self.K, self.Lsamp), np.float32)
         yf = self.empty((self.R, self.K, self.T, self.F), np.complex64)
         self._chk(self.lib.disco_tango_enhance_iterated(self.ctx, py, pmz, pmw, iters, out.ptr, None, yf.ptr, None, 0, self.stream))
@@ -890,7 +846,7 @@ class Engine:
         ps, ks = self.to_device(s, np.float32)
         pn, kn = self.to_device(n, np.float32)
         pmz, kmz = self.to_device(mask_z, np.float32)
-        pmw, kmw = (pmz, kmz) if (mask_w is mask_z and mask_z is not None) else self.to_device(mask_w, np.float32)
+        pmw, kmw = self._alias(mask_w, mask_z, (pmz, kmz), np.float32, none='null')         # None is the oracle mask, not mask_z
         bufs = {nm: self.empty((self.R, self.K, self.T, self.F), np.float32 if nm.startswith('mask') else np.complex64) for nm in names}
         outs = L.DiscoRefOutputs(**{nm: b.ptr for nm, b in bufs.items()})
         self._chk(self.lib.disco_tango_reference(self.ctx, py, ps, pn, pmz, pmw, L.MASK_FOR_Z[mask_for_z], steps, C.byref(outs), None, 0,
@@ -905,19 +861,13 @@ class Engine:
         """y (R,K,M,L), masks (R,K,T,F) -> out (R,K,L) [, z_y, yf (R,K,T,F)]: offline_tango's y branch + iSTFT."""
         py, ky = self.to_device(y, np.float32)
         pmz, kmz = self.to_device(mask_z, np.float32)
-        if mask_w is None or mask_w is mask_z:
-            pmw, kmw = pmz, kmz
-        else:
-            pmw, kmw = self.to_device(mask_w, np.float32)
-        if out is None:
-            out = self.empty((self.R, self.K, self.Lsamp), np.float32)
-        po, ko = self.to_device(out, np.float32)
+        pmw, kmw = self._alias(mask_w, mask_z, (pmz, kmz), np.float32, none='same')
+        out, po, ko = self._out(out, (self.R, self.K, self.Lsamp), np.float32, 'any')
         z = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_z else None
         yf = self.empty((self.R, self.K, self.T, self.F), np.complex64) if want_yf else None
-        pws, kws = (None, None) if workspace is None else self.to_device(workspace, np.uint8)
+        pws, kws = self.to_device(workspace, np.uint8)
         wsb = 0 if workspace is None else (workspace.nbytes if hasattr(workspace, 'nbytes') else workspace.numel())
-        self._chk(self.lib.disco_tango_enhance(self.ctx, py, pmz, pmw, po, z.ptr if z else None, yf.ptr if yf else None,
-                                               pws, wsb, self.stream))
+        self._chk(self.lib.disco_tango_enhance(self.ctx, py, pmz, pmw, po, _ptr(z), _ptr(yf), pws, wsb, self.stream))
         return out, z, yf
 
 
@@ -949,10 +899,7 @@ class _OnlineStream:
                 assert tuple(mk.shape) == (R, K, n_new, e.F), f'{nm}: expected {(R, K, n_new, e.F)} (n_hops + 1 frames with last=True), got {tuple(mk.shape)}'
         py, ky = e.to_device(np.ascontiguousarray(y_new) if isinstance(y_new, np.ndarray) else y_new, np.float32)
         pmz, kmz = e.to_device(mask_z, np.float32)
-        if mask_w is None or mask_w is mask_z:
-            pmw, kmw = pmz, kmz
-        else:
-            pmw, kmw = e.to_device(mask_w, np.float32)
+        pmw, kmw = e._alias(mask_w, mask_z, (pmz, kmz), np.float32, none='same')
         need = int(e.lib.disco_online_stream_workspace_bytes(e.ctx, n_hops))
         if self.ws is None or self.ws.nbytes < need:
             self.ws = e.empty((need,), np.uint8)
