@@ -109,45 +109,73 @@ bool overlap_applies(const disco_ctx* ctx) {
     return o >= 2 || (long long)ctx->cfg.rooms * ctx->cfg.nodes >= 1024;
 }
 
+// What child h takes from its parent, piece by piece, and what it drops with each piece.  The one statement of "and the same for both
+// children": ensure_halves applies all of it to a new child, each setter the piece it changed.
+void child_follow(const disco_ctx* parent, int h, int what) {
+    disco_ctx* ch = parent->half[h];
+    if (what & FOLLOW_TUNING) {
+        ch->geom_rooms = parent->cfg.rooms;                // the launch geometry of the whole batch
+        ch->tune_runw = parent->tune_runw;
+        ch->tune_cov_chunks = parent->tune_cov_chunks;
+        ch->tune_step2_chunks = parent->tune_step2_chunks;
+        ch->tune_pairs = parent->tune_pairs;
+        partials_forget(ch);                               // partial sums of another geometry must not be re-used
+    }
+    if (what & FOLLOW_OPTIONS) {                           // (drops nothing)
+        for (int i = 0; i < DISCO_N_OPTIONS; ++i) ch->opt[i] = parent->opt[i];
+        ch->opt[DISCO_OPT_OVERLAP_SOLVES] = 0;
+    }
+    if (what & FOLLOW_STAGES) {
+        stage_clear(ch);
+        ch->stage_on = parent->stage_on;
+    }
+    if (what & FOLLOW_LENGTHS) {                           // its slice of the lengths (the device block stays the parent's), or none
+        const int r0 = child_room0(parent, h);
+        if (has_lengths(parent)) ch->h_lens.assign(parent->h_lens.begin() + r0, parent->h_lens.begin() + r0 + ch->cfg.rooms);
+        else ch->h_lens.clear();
+        ch->d_lens = has_lengths(parent) ? parent->d_lens + r0 : nullptr;
+        partials_forget(ch);                               // partial sums / reference state of other lengths must not be re-used
+        ch->ref_ws = nullptr;
+    }
+}
+
+// (the children only: what ensure_halves needs for its new ones)
+static int reserve_children(disco_ctx* ctx) {
+    int rc = 0;
+    for_children(ctx, [&](disco_ctx* ch, int) {
+        if (!rc && (rc = reserve_scratch(ch))) lift_child_error(ctx, ch, rc);
+    });
+    return rc;
+}
+
+int reserve_family(disco_ctx* ctx) {
+    const int rc = reserve_scratch(ctx);
+    return rc ? rc : reserve_children(ctx);
+}
+
 int ensure_halves(disco_ctx* ctx) {
     if (!overlap_applies(ctx) || ctx->half[0]) return 0;
-    const int ra = ctx->cfg.rooms / 2, rb = ctx->cfg.rooms - ra;
     // both children or none: a failure part-way (out of memory for the second child's blocks) must not leave half[0] set and
     // half[1] NULL -- the next call would return early on half[0] and the overlapped route would dereference the missing one
     auto drop = [ctx](int rc, const char* msg) {
         char keep[sizeof(ctx->err)];
         snprintf(keep, sizeof(keep), "%s", msg);
-        for (int h = 0; h < 2; ++h) {
-            if (ctx->half[h]) disco_destroy(ctx->half[h]);
-            ctx->half[h] = nullptr;
-        }
+        for_children(ctx, [](disco_ctx* ch, int) { disco_destroy(ch); });
+        ctx->half[0] = ctx->half[1] = nullptr;
         return fail(ctx, rc, keep);
     };
     for (int h = 0; h < 2; ++h) {
         disco_cfg c = ctx->cfg;
-        c.rooms = h ? rb : ra;
+        c.rooms = h ? ctx->cfg.rooms - child_room0(ctx, 1) : child_room0(ctx, 1);
         c.flags |= DISCO_FLAG_NO_CHILDREN | DISCO_FLAG_LAZY_SCRATCH;
-        disco_ctx* ch = nullptr;
-        const int rc = disco_create(&ch, &c);
+        const int rc = disco_create(&ctx->half[h], &c);
         if (rc) return drop(rc, disco_last_error(nullptr));
-        ch->parent = ctx;
-        ch->geom_rooms = ctx->cfg.rooms;                   // the launch geometry of the whole batch
-        ch->tune_runw = ctx->tune_runw;
-        ch->tune_cov_chunks = ctx->tune_cov_chunks;
-        ch->tune_step2_chunks = ctx->tune_step2_chunks;
-        ch->tune_pairs = ctx->tune_pairs;
-        for (int i = 0; i < DISCO_N_OPTIONS; ++i) ch->opt[i] = ctx->opt[i];
-        ch->opt[DISCO_OPT_OVERLAP_SOLVES] = 0;
-        ch->stage_on = ctx->stage_on;
-        ctx->half[h] = ch;
-        if (has_lengths(ctx)) {                            // its slice of the lengths (the device block stays the parent's)
-            ch->h_lens.assign(ctx->h_lens.begin() + (h ? ra : 0), ctx->h_lens.begin() + (h ? ra + rb : ra));
-            ch->d_lens = ctx->d_lens + (h ? ra : 0);
-        }
-        if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) {
-            const int rs = reserve_scratch(ch);
-            if (rs) return drop(rs, ch->err);
-        }
+        ctx->half[h]->parent = ctx;
+        child_follow(ctx, h, FOLLOW_ALL);
+    }
+    if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) {
+        const int rs = reserve_children(ctx);
+        if (rs) return drop(rs, ctx->err);
     }
     if (!ctx->side_stream) {
         HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
@@ -161,7 +189,7 @@ int ensure_halves(disco_ctx* ctx) {
 extern "C" void disco_destroy(disco_ctx* ctx) {
     if (!ctx) return;
     DevGuard dev_guard_(ctx->cfg.device);
-    for (int h = 0; h < 2; ++h) disco_destroy(ctx->half[h]);
+    for_children(ctx, [](disco_ctx* ch, int) { disco_destroy(ch); });
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -193,21 +221,16 @@ extern "C" int disco_set_lengths(disco_ctx* ctx, const int32_t* lengths, int n_r
     DISCO_ENTER(ctx);
     const disco_cfg& c = ctx->cfg;
     if (ctx->parent) return fail(ctx, DISCO_E_ARG, "disco_set_lengths: a half-batch child follows its parent");
-    auto drop_state = [](disco_ctx* x) {                   // partial sums / reference state of other lengths must not be re-used
-        partials_forget(x);
-        x->ref_ws = nullptr;
+    auto changed = [ctx] {                                 // partial sums / reference state of other lengths must not be re-used
+        partials_forget(ctx);
+        ctx->ref_ws = nullptr;
+        for_children(ctx, [ctx](disco_ctx*, int h) { child_follow(ctx, h, FOLLOW_LENGTHS); });
+        return 0;
     };
     if (!lengths) {
         ctx->h_lens.clear();
         ctx->d_lens = nullptr;
-        drop_state(ctx);
-        for (int h = 0; h < 2; ++h)
-            if (ctx->half[h]) {
-                ctx->half[h]->h_lens.clear();
-                ctx->half[h]->d_lens = nullptr;
-                drop_state(ctx->half[h]);
-            }
-        return 0;
+        return changed();
     }
     if (n_rooms != c.rooms) return fail(ctx, DISCO_E_ARG, "disco_set_lengths: n_rooms must equal cfg.rooms");
     if (sharded(ctx)) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_set_lengths: per-room lengths are not supported under a node shard");
@@ -223,28 +246,14 @@ extern "C" int disco_set_lengths(disco_ctx* ctx, const int32_t* lengths, int n_r
     HIPCHK(ctx, hipMemcpy(ctx->d_lens_own, lengths, (size_t)c.rooms * sizeof(int), hipMemcpyHostToDevice));
     ctx->h_lens.assign(lengths, lengths + n_rooms);
     ctx->d_lens = ctx->d_lens_own;
-    drop_state(ctx);
-    int r0 = 0;
-    for (int h = 0; h < 2; ++h)
-        if (ctx->half[h]) {
-            const int rh = ctx->half[h]->cfg.rooms;
-            ctx->half[h]->h_lens.assign(lengths + r0, lengths + r0 + rh);
-            ctx->half[h]->d_lens = ctx->d_lens_own + r0;
-            drop_state(ctx->half[h]);
-            r0 += rh;
-        }
-    return 0;
+    return changed();
 }
 
 extern "C" int disco_stage_timing(disco_ctx* ctx, int enable) {
     DISCO_ENTER(ctx);
     stage_clear(ctx);
     ctx->stage_on = enable != 0;
-    for (int h = 0; h < 2; ++h)
-        if (ctx->half[h]) {
-            stage_clear(ctx->half[h]);
-            ctx->half[h]->stage_on = ctx->stage_on;
-        }
+    for_children(ctx, [ctx](disco_ctx*, int h) { child_follow(ctx, h, FOLLOW_STAGES); });
     return 0;
 }
 
@@ -254,9 +263,7 @@ extern "C" int disco_stage_report(disco_ctx* ctx, char* names, float* total_ms, 
         return fail(ctx, DISCO_E_ARG, "disco_stage_report: bad argument");
     int n = 0;
     // the context's own records, then those of its half-batch children merged in by name
-    disco_ctx* src[3] = {ctx, ctx->half[0], ctx->half[1]};
-    for (disco_ctx* c : src) {
-        if (!c) continue;
+    auto merge = [&](disco_ctx* c) -> int {
         for (auto& st : c->stages) {
             float ms = 0.f;
             for (auto& e : st.evs) {
@@ -280,8 +287,11 @@ extern "C" int disco_stage_report(disco_ctx* ctx, char* names, float* total_ms, 
             launches[at] += (int)st.evs.size();
             if (rooms) rooms[at] += (int64_t)st.evs.size() * c->cfg.rooms;
         }
-    }
-    return n;
+        return 0;
+    };
+    int rc = 0;
+    for_family(ctx, [&](disco_ctx* c) { if (!rc) rc = merge(c); });
+    return rc ? rc : n;
 }
 
 extern "C" int disco_set_tuning(disco_ctx* ctx, int stft_frames_per_wave, int cov_chunks, int step2_chunks, int istft_pairs) {
@@ -294,16 +304,8 @@ extern "C" int disco_set_tuning(disco_ctx* ctx, int stft_frames_per_wave, int co
     ctx->tune_step2_chunks = step2_chunks;
     ctx->tune_pairs = istft_pairs;
     partials_forget(ctx);              // partial sums of another geometry must not be re-used
-    for (int h = 0; h < 2; ++h)
-        if (ctx->half[h]) {
-            const int rc = disco_set_tuning(ctx->half[h], stft_frames_per_wave, cov_chunks, step2_chunks, istft_pairs);
-            if (rc) return fail(ctx, rc, ctx->half[h]->err);
-            if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) {
-                const int rs = reserve_scratch(ctx->half[h]);
-                if (rs) return fail(ctx, rs, ctx->half[h]->err);
-            }
-        }
-    if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) return reserve_scratch(ctx);     // the new geometry may need larger blocks
+    for_children(ctx, [ctx](disco_ctx*, int h) { child_follow(ctx, h, FOLLOW_TUNING); });
+    if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) return reserve_family(ctx);      // the new geometry may need larger blocks
     return 0;
 }
 
@@ -335,16 +337,10 @@ extern "C" int disco_set_option(disco_ctx* ctx, const char* key, int value) {
     if (i < 0) return fail(ctx, DISCO_E_ARG, "disco_set_option: unknown key");
     ctx->opt[i] = value;
     if (i == DISCO_OPT_OVERLAP_SOLVES) return disco_host::ensure_halves(ctx);     // (may allocate: this is not a compute call)
-    for (int h = 0; h < 2; ++h)
-        if (ctx->half[h]) ctx->half[h]->opt[i] = value;
+    for_children(ctx, [ctx](disco_ctx*, int h) { child_follow(ctx, h, FOLLOW_OPTIONS); });
     // a route may ask for larger partial-sum blocks than the one sized so far (e.g. "room_dma" 0: chunked sums): size them HERE, so
     // that the next compute call still allocates nothing (this is not a compute call)
-    if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) {
-        int rc = disco_host::reserve_scratch(ctx);
-        for (int h = 0; h < 2 && !rc; ++h)
-            if (ctx->half[h] && (rc = disco_host::reserve_scratch(ctx->half[h]))) return fail(ctx, rc, ctx->half[h]->err);
-        return rc;
-    }
+    if (!(ctx->cfg.flags & DISCO_FLAG_LAZY_SCRATCH)) return reserve_family(ctx);
     return 0;
 }
 

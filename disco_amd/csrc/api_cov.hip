@@ -75,21 +75,20 @@ static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* ma
     const disco_cfg& c = ctx->cfg;
     const int M = c.mics, KR = P - M;
     const int chunks = cov_chunks(ctx);
-    const long long G = (long long)c.rooms * ctx->Kl;
-    const int NP = P * (P + 1) / 2, tiles = (ctx->F - 1 + 63) / 64;
+    const SumsPlan plan{(long long)c.rooms * ctx->Kl, chunks, chunks, P, false};
+    const int tiles = (ctx->F - 1 + 63) / 64;
     const int nbg = (cov_wide_blocks(P) + CW_WAVES - 1) / CW_WAVES;
-    const long long n_items = G * (tiles + 1) * chunks * nbg;
-    const long long grid = xcd_grid(n_items);
+    const long long grid = xcd_grid(plan.G * (tiles + 1) * chunks * nbg);
     if (grid > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: batch too large (P > 16: more than 2^31 workgroups)");
-    // the block this batch needs, G x chunks x F x NP x 16 B, checked before anything runs
-    const size_t need = (size_t)G * chunks * ctx->F * NP * sizeof(float4);
+    // the block this batch needs is checked before anything runs
     int rc = 0;
-    float4* part = partials_begin(ctx, need, false, &rc);
+    float4* part = partials_begin(ctx, plan, &rc);
     if (rc) {
         (void)hipGetLastError();
         char m[400];
         snprintf(m, sizeof(m), "disco_cov_masked: P = %d needs %.2f GiB of partial-sum scratch (%lld units x %d chunks x %d bins x %d pairs "
-                 "x 16 B), which the device cannot provide: split the batch into fewer rooms", P, need / 1073741824.0, G, chunks, ctx->F, NP);
+                 "x 16 B), which the device cannot provide: split the batch into fewer rooms", P, plan.bytes(ctx->F) / 1073741824.0, plan.G, chunks,
+                 ctx->F, plan.pairs());
         return fail(ctx, DISCO_E_UNSUPPORTED, m);
     }
     const CovArgs a = cov_args(ctx, X, mask, Zs, Zn, part, chunks, mask_remote);
@@ -97,7 +96,7 @@ static int cov_partials_wide(disco_ctx* ctx, const disco_c32* X, const float* ma
         constexpr bool SAMEZ = decltype(samez)::value;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_wide<SAMEZ>), dim3((unsigned)grid), dim3(64 * CW_WAVES), 0, (hipStream_t)s, a, M, KR);
     });
-    partials_commit(ctx, chunks, P, false);
+    partials_commit(ctx, plan);
     return check_launch(ctx, "k_cov_wide");
 }
 
@@ -118,19 +117,16 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
     if (M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: M > 8 mics per node not supported");
     if (P > CW_PMAX) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_cov_masked: P = M + K - 1 > 32 not supported");
     if (P > CB_PMAX) return cov_partials_wide(ctx, X, mask, Zs, Zn, mask_remote, P, s);
-    int chunks = cov_chunks(ctx);
-    const long long G = (long long)c.rooms * ctx->Kl;
-    const int NP = P * (P + 1) / 2;
     const bool same = (Zs == Zn);
     const bool split = (KR == 0 || (P > 8 && same && mask_remote && (ctx->F - 1) % 64 == 0)) && cov_split_shape(M, KR);
     // step-1 shapes of the split kernels (KR = 0, M >= 7): float64 accumulators, every frame chunk leaves a (hi, lo) PAIR of partial blocks
     const bool f64 = split && KR == 0;
-    if (f64) chunks = cov1_f64_chunks(ctx);
-    const int blocks = f64 ? 2 * chunks : chunks;
-    const size_t need = (size_t)G * blocks * ctx->F * NP * sizeof(float4);
+    const int chunks = f64 ? cov1_f64_chunks(ctx) : cov_chunks(ctx);
     skiploc = skiploc && split && KR > 0 && step1_held(ctx, X, mask);
+    const SumsPlan plan{(long long)c.rooms * ctx->Kl, chunks, f64 ? 2 * chunks : chunks, P, skiploc};
+    const long long G = plan.G;
     int rc = 0;
-    float4* part = partials_begin(ctx, need, skiploc, &rc);
+    float4* part = partials_begin(ctx, plan, &rc);
     if (rc) return rc;
     const CovArgs a = cov_args(ctx, X, mask, Zs, Zn, part, chunks, mask_remote);
     const hipStream_t st = (hipStream_t)s;
@@ -154,10 +150,35 @@ int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const di
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov_big<SAMEZ>), dim3((unsigned)nblk), dim3(64 * CB_S), 0, st, a, M, KR);
             });
     }
-    partials_commit(ctx, blocks, P, skiploc);
+    partials_commit(ctx, plan);
     // step-1 sums (P == M, all nodes here) can be re-used by a step 2 on the same mask
     if (KR == 0 && !sharded(ctx)) step1_keep(ctx, X, mask);
     return check_launch(ctx, "k_cov");
+}
+
+// Both partial-sum blocks at the largest size any covariance call of this context can ask for with the present geometry: the plan of the
+// widest pencil (P = M + K - 1) with the largest of the chunk counts above and of the other units (stft_cov_chunks, step2_chunks,
+// room_chunks).  Pairing the largest count with the widest pencil over-sizes; the sizes are kept (tests/test_partials_state_emulated.py).
+int reserve_scratch(disco_ctx* ctx) {
+    const disco_cfg& c = ctx->cfg;
+    const long long G = (long long)c.rooms * ctx->Kl;
+    const int P2 = c.mics + c.nodes - 1;
+    auto bytes = [&](int chunks, int P) { return SumsPlan{G, chunks, chunks, P, false}.bytes(ctx->F); };
+    if (P2 > CB_PMAX && P2 <= CW_PMAX && c.mics <= 8) {
+        // 17 <= P <= 32: step 1 (P = M, the chunk counts below) and step 2 (k_cov_wide, cov_chunks) size the full block; the tail block
+        // only ever pairs with re-used step-1 sums, which the wide route does not take
+        int ch1 = cov_chunks(ctx);
+        if (c.mics >= 7) ch1 = std::max(ch1, 2 * cov1_f64_chunks(ctx));
+        ch1 = std::max(ch1, stft_cov_chunks(ctx, nullptr));
+        const size_t need1 = bytes(ch1, c.mics);
+        return partials_reserve(ctx, std::max(need1, bytes(cov_chunks(ctx), P2)), need1);
+    }
+    int chunks = std::max(cov_chunks(ctx), step2_chunks(ctx, (ctx->F - 1) / 64 + 1));
+    if (c.mics >= 7) chunks = std::max(chunks, 2 * cov1_f64_chunks(ctx));                       // the (hi, lo) pairs of k_cov_loc_f64
+    if (c.mics <= 8) chunks = std::max(chunks, stft_cov_chunks(ctx, nullptr));
+    if (P2 > 8) chunks = std::max(chunks, room_chunks(ctx));
+    const size_t need = bytes(chunks, std::min(P2, 16));
+    return partials_reserve(ctx, need, need);
 }
 }  // namespace disco_host
 
@@ -165,10 +186,7 @@ extern "C" int disco_cov_masked(disco_ctx* ctx, const disco_c32* X, const float*
                                 const disco_c32* Zn, int mask_remote, int P, disco_c32* Rss, disco_c32* Rnn,
                                 disco_stream s) {
     DISCO_ENTER(ctx);
-    if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_cov_masked: Rss and Rnn must both be given or both be NULL");
-    int rc = cov_partials(ctx, X, mask, Zs, Zn, mask_remote, P, s);
-    if (rc || !Rss) return rc;
-    return cov_finalize(ctx, Rss, Rnn, s);
+    return cov_pass_entry(ctx, "disco_cov_masked", Rss, Rnn, s, [&] { return cov_partials(ctx, X, mask, Zs, Zn, mask_remote, P, s); });
 }
 
 // test-only (include/disco_hip.h): cov_finalize for whatever is pending, two-block pencils included

@@ -35,7 +35,8 @@ void partials_forget(disco_ctx* ctx) {
     step1_drop(ctx);
 }
 
-float4* partials_begin(disco_ctx* ctx, size_t bytes, bool tail, int* rc) {
+// the full or the tail block, `bytes` large: a block that has to grow takes the records of its contents with it (host.h)
+static float4* block_of(disco_ctx* ctx, size_t bytes, bool tail, int* rc) {
     Partials& ps = ctx->partials;
     DevBlock& b = tail ? ps.tail : ps.full;
     if (b.bytes < bytes) {
@@ -46,11 +47,13 @@ float4* partials_begin(disco_ctx* ctx, size_t bytes, bool tail, int* rc) {
     return *rc ? nullptr : (float4*)b.p;
 }
 
-void partials_commit(disco_ctx* ctx, int blocks, int P, bool tail) {
-    ctx->partials.pend_blocks = blocks;
-    ctx->partials.pend_P = P;
-    ctx->partials.pend_tail = tail;
-    if (!tail) step1_drop(ctx);
+float4* partials_begin(disco_ctx* ctx, const SumsPlan& plan, int* rc) { return block_of(ctx, plan.bytes(ctx->F), plan.tail, rc); }
+
+void partials_commit(disco_ctx* ctx, const SumsPlan& plan) {
+    ctx->partials.pend_blocks = plan.blocks;
+    ctx->partials.pend_P = plan.P;
+    ctx->partials.pend_tail = plan.tail;
+    if (!plan.tail) step1_drop(ctx);
 }
 
 void step1_keep(disco_ctx* ctx, const void* X, const void* mask) {
@@ -81,8 +84,8 @@ bool partials_pending(const disco_ctx* ctx, PendingSums* out) {
 
 int partials_reserve(disco_ctx* ctx, size_t full_bytes, size_t tail_bytes) {
     int rc = 0;
-    partials_begin(ctx, full_bytes, false, &rc);
-    if (!rc) partials_begin(ctx, tail_bytes, true, &rc);
+    block_of(ctx, full_bytes, false, &rc);
+    if (!rc) block_of(ctx, tail_bytes, true, &rc);
     return rc;
 }
 

@@ -13,23 +13,26 @@ using namespace disco_host;
 // ---------------------------------------------------------------------------------------------------------
 // whole path
 // ---------------------------------------------------------------------------------------------------------
+// where child h's slice of an overlapped call's workspace starts: child 1's behind child 0's
+static size_t child_ws_offset(const disco_ctx* ctx, int h) { return h ? align_up(ws_layout(ctx->half[0]).total) : 0; }
+
 namespace disco_host {
 WsLayout ws_layout(const disco_ctx* ctx) {
     const disco_cfg& c = ctx->cfg;
     const size_t G = (size_t)c.rooms * c.nodes, TF = (size_t)ctx->T * ctx->F;
     const size_t Pmax = (size_t)c.mics + c.nodes - 1;
     WsLayout l;
-    size_t o = 0;
-    l.X = o;   o = align_up(o + G * TF * c.mics * sizeof(c32));
-    l.z = o;   o = align_up(o + G * TF * sizeof(c32));
-    l.yf = o;  o = align_up(o + G * TF * sizeof(c32));
-    l.Rss = o; o = align_up(o + G * ctx->F * Pmax * Pmax * sizeof(c32));
-    l.Rnn = o; o = align_up(o + G * ctx->F * Pmax * Pmax * sizeof(c32));
-    l.w = o;   o = align_up(o + G * ctx->F * Pmax * sizeof(c32));
-    l.w2 = o;  o = align_up(o + G * ctx->F * Pmax * sizeof(c32));
-    l.total = o;
-    // an overlapped call hands each half-batch child its own slice: the two slices must fit
-    if (ctx->half[0] && ctx->half[1]) l.total = std::max(l.total, align_up(ws_layout(ctx->half[0]).total) + ws_layout(ctx->half[1]).total);
+    Take take;
+    l.X = take(G * TF * c.mics * sizeof(c32));
+    l.z = take(G * TF * sizeof(c32));
+    l.yf = take(G * TF * sizeof(c32));
+    l.Rss = take(G * ctx->F * Pmax * Pmax * sizeof(c32));
+    l.Rnn = take(G * ctx->F * Pmax * Pmax * sizeof(c32));
+    l.w = take(G * ctx->F * Pmax * sizeof(c32));
+    l.w2 = take(G * ctx->F * Pmax * sizeof(c32));
+    l.total = take.o;
+    // an overlapped call hands each half-batch child its own slice (child_args): the two slices must fit
+    if (ctx->half[0] && ctx->half[1]) l.total = std::max(l.total, child_ws_offset(ctx, 1) + ws_layout(ctx->half[1]).total);
     return l;
 }
 }  // namespace disco_host
@@ -74,7 +77,7 @@ int run_pipelined(disco_ctx* ctx, Steps (&steps)[2], disco_stream s) {
     for (int h = 0; h < 2 && !rc; ++h)
         for (size_t i = 0; i < n && !rc; ++i) {
             rc = run_step(ctx->half[h], steps[h][i], (disco_stream)(h ? s1 : s0));
-            if (rc) snprintf(ctx->err, sizeof(ctx->err), "%.500s", ctx->half[h]->err);
+            if (rc) lift_child_error(ctx, ctx->half[h], rc);
         }
     const hipError_t e1 = hipEventRecord(ctx->ev_join, s1), e2 = hipStreamWaitEvent(s0, ctx->ev_join, 0);       // the join, whatever happened above
     if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) {
@@ -94,7 +97,7 @@ struct PathArgs {
 // the slice of the caller's arrays / workspace that child h (rooms [r0, r0 + rooms_h)) works on
 PathArgs child_args(const disco_ctx* ctx, const PathArgs& a, int h) {
     const disco_cfg& c = ctx->cfg;
-    const size_t r0 = h ? (size_t)ctx->half[0]->cfg.rooms : 0;
+    const size_t r0 = (size_t)child_room0(ctx, h);
     const size_t K = c.nodes, TF = (size_t)ctx->T * ctx->F, sy = K * c.mics * c.length, sm = K * TF, so = K * c.length;
     PathArgs b;
     b.y = a.y + r0 * sy;
@@ -103,8 +106,19 @@ PathArgs child_args(const disco_ctx* ctx, const PathArgs& a, int h) {
     b.out = a.out + r0 * so;
     b.z_y = a.z_y ? a.z_y + r0 * sm : nullptr;
     b.yf = a.yf ? a.yf + r0 * sm : nullptr;
-    b.ws = a.ws + (h ? align_up(ws_layout(ctx->half[0]).total) : 0);
+    b.ws = a.ws + child_ws_offset(ctx, h);
     return b;
+}
+
+// the arrays of one (half-)batch of a whole-path call: X, w, w2 in this context's workspace; z and the filtered spectra yo in the
+// caller's z_y / yf where given, else in the workspace too
+struct PathBufs {
+    disco_c32 *X, *z, *yo, *w, *w2;
+};
+PathBufs path_bufs(const disco_ctx* ctx, const PathArgs& a) {
+    const WsLayout l = ws_layout(ctx);
+    auto at = [&](size_t off) { return (disco_c32*)(a.ws + off); };
+    return {at(l.X), a.z_y ? a.z_y : at(l.z), a.yf ? a.yf : at(l.yf), at(l.w), at(l.w2)};
 }
 }  // namespace
 
@@ -112,47 +126,20 @@ extern "C" size_t disco_workspace_bytes(const disco_ctx* ctx) { return ctx ? ws_
 
 namespace disco_host {
 // caller's workspace if given (size-checked), else the context's own (grown on demand)
-int acquire_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, const WsLayout& l, char** ws_out, const char* who) {
-    char* ws = (char*)workspace;
-    if (ws) {
-        if (workspace_bytes < l.total) {
-            std::string m = std::string(who) + ": workspace too small";
-            return fail(ctx, DISCO_E_ARG, m.c_str());
-        }
-    } else {
-        const int rc = ensure_own_ws(ctx, l.total);
-        if (rc) return rc;
-        ws = (char*)ctx->own_ws.p;
+int locate_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, size_t need, char** ws_out, const char* who) {
+    if (workspace) {
+        if (workspace_bytes < need) return fail(ctx, DISCO_E_ARG, (std::string(who) + ": workspace too small").c_str());
+        *ws_out = (char*)workspace;
+        return 0;
     }
-    if (ctx->ref_ws == ws) ctx->ref_ws = nullptr;      // a steps = 1 state of disco_tango_reference in this workspace is overwritten
-    *ws_out = ws;
-    return 0;
+    const int rc = ensure_own_ws(ctx, need);
+    *ws_out = (char*)ctx->own_ws.p;
+    return rc;
 }
-// Both partial-sum blocks at the largest size any covariance call of this context can ask for with the present geometry:
-// [R * Kl][chunks][F][P (P + 1) / 2] float4 with P = M + K - 1 and the largest of the three chunk counts.
-int reserve_scratch(disco_ctx* ctx) {
-    const disco_cfg& c = ctx->cfg;
-    const size_t G = (size_t)c.rooms * ctx->Kl;
-    const int P2 = c.mics + c.nodes - 1;
-    if (P2 > CB_PMAX && P2 <= CW_PMAX && c.mics <= 8) {
-        // 17 <= P <= 32: step 1 (P = M, the chunk counts below) and step 2 (k_cov_wide, cov_chunks) size the full block; the tail block
-        // only ever pairs with re-used step-1 sums, which the wide route does not take
-        const size_t NP1 = (size_t)c.mics * (c.mics + 1) / 2, NP2 = (size_t)P2 * (P2 + 1) / 2;
-        int ch1 = cov_chunks(ctx);
-        if (c.mics >= 7) ch1 = std::max(ch1, 2 * cov1_f64_chunks(ctx));
-        ch1 = std::max(ch1, stft_cov_chunks(ctx, nullptr));
-        const size_t need1 = G * (size_t)ch1 * ctx->F * NP1 * sizeof(float4);
-        const size_t need2 = G * (size_t)cov_chunks(ctx) * ctx->F * NP2 * sizeof(float4);
-        return partials_reserve(ctx, std::max(need1, need2), need1);
-    }
-    const size_t P = (size_t)std::min(P2, 16);
-    const size_t NP = P * (P + 1) / 2;
-    int chunks = std::max(cov_chunks(ctx), step2_chunks(ctx, (ctx->F - 1) / 64 + 1));
-    if (c.mics >= 7) chunks = std::max(chunks, 2 * cov1_f64_chunks(ctx));                       // the (hi, lo) pairs of k_cov_loc_f64
-    if (c.mics <= 8) chunks = std::max(chunks, stft_cov_chunks(ctx, nullptr));
-    if (c.mics + c.nodes - 1 > 8) chunks = std::max(chunks, room_chunks(ctx));
-    const size_t need = G * (size_t)chunks * ctx->F * NP * sizeof(float4);
-    return partials_reserve(ctx, need, need);
+int acquire_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, const WsLayout& l, char** ws_out, const char* who) {
+    const int rc = locate_ws(ctx, workspace, workspace_bytes, l.total, ws_out, who);
+    if (!rc && ctx->ref_ws == *ws_out) ctx->ref_ws = nullptr;      // a steps = 1 state of disco_tango_reference in this workspace is overwritten
+    return rc;
 }
 }  // namespace disco_host
 
@@ -160,6 +147,11 @@ int reserve_scratch(disco_ctx* ctx) {
 static bool fused_route(const disco_ctx* ctx) {
     const disco_cfg& c = ctx->cfg;
     return c.nodes > 1 && c.mics + c.nodes - 1 <= 8 && !(c.flags & DISCO_FLAG_STAGED_STEP2);
+}
+// ... and it ends in ONE filter + iSTFT pass, yf staying on chip: yf not asked for, 512 points, a shape the kernel takes.  Decides the tail
+// of disco_tango_enhance, and with it what may be left out of X and the layout of its rows (enhance_steps)
+static bool fused_tail_one_pass(const disco_ctx* ctx, const disco_c32* yf) {
+    return fused_route(ctx) && !yf && ctx->cfg.n_fft == 512 && step2_apply_istft_ok(ctx);
 }
 
 // exchange + step-2 statistics with z materialised, mask_for_z = 'local': ONE pass over X for every node of a room where the shape and the
@@ -231,15 +223,11 @@ static int run_path(disco_ctx* ctx, const PathArgs& a, bool overlap, const std::
 // offline_tango's y branch as a list of steps (tango.py:326-450 + 528); `a` names this context's slice of the batch
 static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
     const disco_cfg& c = ctx->cfg;
-    const WsLayout l = ws_layout(ctx);
     const float *y = a.y, *mask_z = a.mask_z, *mask_w = a.mask_w;
     float* out = a.out;
     disco_c32 *z_y = a.z_y, *yf = a.yf;
-    disco_c32* X = (disco_c32*)(a.ws + l.X);
-    disco_c32* z = z_y ? z_y : (disco_c32*)(a.ws + l.z);
-    disco_c32* yo = yf ? yf : (disco_c32*)(a.ws + l.yf);
-    disco_c32* w = (disco_c32*)(a.ws + l.w);
-    disco_c32* w2 = (disco_c32*)(a.ws + l.w2);
+    const PathBufs b = path_bufs(ctx, a);
+    disco_c32 *X = b.X, *z = b.z, *yo = b.yo, *w = b.w, *w2 = b.w2;      // (named: the step lambdas capture them by value)
     const int64_t G = (int64_t)c.rooms * c.nodes;
     const int M = c.mics;
     const bool same_mask = mask_w == mask_z;
@@ -258,11 +246,12 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
     // step 1 (tango.py:326-376): STFT + covariance in one pass, solve straight from the partial sums
     // per-room lengths: both readers of X on the fused route without yf (k_step2_cov_fused, k_step2_apply_istft) stop at a room's own
     // frames, so the frames of X beyond them need not be written; every other route reads them and finds the zeros it relies on
-    const bool x_zeros = !(fused_route(ctx) && !yf && c.n_fft == 512 && step2_apply_istft_ok(ctx));
+    const bool one_pass_tail = fused_tail_one_pass(ctx, yf);
+    const bool x_zeros = !one_pass_tail;
     // ... and on that branch X never leaves the workspace, so its rows may take the packed layout ("packed_x", k_stft.h k_stft_cov: [T][F - 1][M],
     // the Nyquist bin in the DC slot): every wave load and store of the three passes over X then covers whole 128-byte lines.  The slot of
     // X in the workspace keeps its size (the packed array is 1 / F smaller), so one workspace serves both values of the option.
-    const XLayout layout = !x_zeros && ctx->opt[DISCO_OPT_PACKED_X] != 0 ? XLayout::Packed : XLayout::Public;
+    const XLayout layout = one_pass_tail && ctx->opt[DISCO_OPT_PACKED_X] != 0 ? XLayout::Packed : XLayout::Public;
     StftCovOpts step1;
     step1.zero_beyond = x_zeros;
     step1.layout = layout;
@@ -276,11 +265,9 @@ static void enhance_steps(disco_ctx* ctx, const PathArgs& a, Steps& st) {
             return step2_cov_partials(ctx, X, mask_w, w, z_y, s, step1_held(ctx, X, mask_w) ? LeadBlock::Step1 : LeadBlock::Accumulate, layout);
         }});
         st.push_back({"solve2", true, solve_pending(w2)});
-        if (!yf && c.n_fft == 512) {   // yf not asked for: filter + iSTFT in one pass, yf stays on chip (shapes the kernel takes)
-            if (step2_apply_istft_ok(ctx)) {
-                st.push_back({"step2_apply_istft", false, [=](disco_stream s) { return step2_apply_istft(ctx, X, w, w2, out, s, layout); }});
-                return;
-            }
+        if (one_pass_tail) {
+            st.push_back({"step2_apply_istft", false, [=](disco_stream s) { return step2_apply_istft(ctx, X, w, w2, out, s, layout); }});
+            return;
         }
         st.push_back({"step2_apply", false, [=](disco_stream s) { return disco_step2_apply_fused(ctx, X, w, w2, nullptr, yo, s); }});
         st.push_back({"istft", false, [=](disco_stream s) { return disco_istft(ctx, yo, G, out, s); }});
@@ -355,16 +342,15 @@ RefLayout ref_layout(const disco_ctx* ctx) {
 extern "C" size_t disco_reference_workspace_bytes(const disco_ctx* ctx) { return ctx ? ref_layout(ctx).total : 0; }
 
 extern "C" size_t disco_owned_bytes(const disco_ctx* ctx) {
-    if (!ctx) return 0;
-    return partials_bytes(ctx) + ctx->own_ws.bytes + ctx->conv_ws.bytes + disco_owned_bytes(ctx->half[0]) + disco_owned_bytes(ctx->half[1]);
+    size_t n = 0;
+    if (ctx) for_family(ctx, [&n](const disco_ctx* x) { n += partials_bytes(x) + x->own_ws.bytes + x->conv_ws.bytes; });
+    return n;
 }
 
 extern "C" int disco_reserve(disco_ctx* ctx, int own_workspace) {
     DISCO_ENTER(ctx);
     if (own_workspace < 0 || own_workspace > 2) return fail(ctx, DISCO_E_ARG, "disco_reserve: own_workspace must be 0, 1 or 2");
-    int rc = reserve_scratch(ctx);
-    for (int h = 0; h < 2 && !rc; ++h)
-        if (ctx->half[h] && (rc = reserve_scratch(ctx->half[h]))) return fail(ctx, rc, ctx->half[h]->err);
+    const int rc = reserve_family(ctx);
     if (rc || !own_workspace) return rc;
     size_t need = ws_layout(ctx).total;
     if (own_workspace == 2) need = std::max(need, ref_layout(ctx).total);
@@ -384,17 +370,13 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
     const int M = c.mics, K = c.nodes, P2 = M + K - 1;
     if (P2 > CW_PMAX || M > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_tango_reference: M + K - 1 > 32 or M > 8 not supported");
     // the workspace: the caller's, or a context-owned one kept in `own_ws` (shared with the enhanced-output entry points)
+    // (located, not acquired: a steps = 2 call continues from the state in it, which is checked first and ends below)
     const RefLayout l = ref_layout(ctx);
-    char* ws = (char*)workspace;
-    if (ws) {
-        if (workspace_bytes < l.total) return fail(ctx, DISCO_E_ARG, "disco_tango_reference: workspace too small");
-    } else {
-        if (ctx->own_ws.bytes < l.total && steps == 2)
-            return fail(ctx, DISCO_E_ARG, "disco_tango_reference: steps = 2 needs the workspace of the preceding steps = 1 call");
-        const int rcw = ensure_own_ws(ctx, l.total);
-        if (rcw) return rcw;
-        ws = (char*)ctx->own_ws.p;
-    }
+    if (!workspace && ctx->own_ws.bytes < l.total && steps == 2)
+        return fail(ctx, DISCO_E_ARG, "disco_tango_reference: steps = 2 needs the workspace of the preceding steps = 1 call");
+    char* ws = nullptr;
+    const int rcw = locate_ws(ctx, workspace, workspace_bytes, l.total, &ws, "disco_tango_reference");
+    if (rcw) return rcw;
     if (steps == 2 && !(ctx->ref_ws == ws && ctx->ref_y == y && ctx->ref_s == s_img && ctx->ref_n == n_img))
         return fail(ctx, DISCO_E_ARG, "disco_tango_reference: steps = 2 needs the state a steps = 1 call with the same y, s, n left in the same "
                                       "workspace (no other whole-path call in between)");
@@ -424,15 +406,14 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
         if (mask_z_in) {
             HIPCHK(ctx, hipMemcpyAsync(mz, mask_z_in, mask_b, hipMemcpyDeviceToDevice, st));
         } else {
-            hipLaunchKernelGGL(k_tf_mask_channel, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)Xs, (const c32*)Xn, mz, nTF, M, c.ref_mic,
-                               c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
+            ew_launch(k_tf_mask_channel, nTF, st, (const c32*)Xs, (const c32*)Xn, mz, nTF, M, c.ref_mic, c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
             if ((rc = check_launch(ctx, "k_tf_mask_channel"))) return rc;
         }
         // ---- step 1: local statistics, filter, compressed signals (tango.py:343-376)
         if (oracle_sigs) {            // s_hat = S, n_hat = N: Rss from the target image alone, Rnn from the noise image alone
-            hipLaunchKernelGGL(k_fill_f32, dim3(ew_grid(nTF)), dim3(256), 0, st, mc, 1.f, nTF);
+            ew_launch(k_fill_f32, nTF, st, mc, 1.f, nTF);
             if ((rc = disco_cov_masked(ctx, Xs, mc, nullptr, nullptr, 0, M, Rss, Rtmp, s))) return rc;      // mask 1: Rss = <S S^H>  (Rtmp = 0)
-            hipLaunchKernelGGL(k_fill_f32, dim3(ew_grid(nTF)), dim3(256), 0, st, mc, 0.f, nTF);
+            ew_launch(k_fill_f32, nTF, st, mc, 0.f, nTF);
             if ((rc = disco_cov_masked(ctx, Xn, mc, nullptr, nullptr, 0, M, Rtmp, Rnn, s))) return rc;      // mask 0: Rnn = <N N^H>  (Rtmp = 0)
             if ((rc = disco_gevd_mwf_r1(ctx, Rss, Rnn, G * ctx->F, M, c.mu, w_loc, nullptr, s))) return rc;
         } else {
@@ -458,8 +439,7 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
     if (mask_w_in) {
         HIPCHK(ctx, hipMemcpyAsync(mw, mask_w_in, mask_b, hipMemcpyDeviceToDevice, st));
     } else {
-        hipLaunchKernelGGL(k_tf_mask_channel, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)Xs, (const c32*)Xn, mw, nTF, M, 0,
-                           c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
+        ew_launch(k_tf_mask_channel, nTF, st, (const c32*)Xs, (const c32*)Xn, mw, nTF, M, 0, c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
         if ((rc = check_launch(ctx, "k_tf_mask_channel"))) return rc;
     }
     if ((rc = give(out->mask_w, mw, mask_b))) return rc;
@@ -471,20 +451,19 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
             case DISCO_MZ_LOCAL: mask_remote = 1; break;
             case DISCO_MZ_NONE: Zn_rows = znres; break;
             case DISCO_MZ_DISTANT:
-                hipLaunchKernelGGL(k_mask_rows, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)zy, (const float*)mw, (c32*)rows_s, (c32*)rows_n, nTF);
+                ew_launch(k_mask_rows, nTF, st, (const c32*)zy, (const float*)mw, (c32*)rows_s, (c32*)rows_n, nTF);
                 Zs_rows = rows_s;
                 Zn_rows = rows_n;
                 break;
             case DISCO_MZ_COMPRESSED: {           // the sender's mask from ITS compressed target / noise (get_mask(z_s, z_n), tango.py:402-403)
-                hipLaunchKernelGGL(k_tf_mask, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)zs, (const c32*)zn_, mc, nTF, c.mask_type,
-                                   c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
-                hipLaunchKernelGGL(k_mask_rows, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)zy, (const float*)mc, (c32*)rows_s, (c32*)rows_n, nTF);
+                ew_launch(k_tf_mask, nTF, st, (const c32*)zs, (const c32*)zn_, mc, nTF, c.mask_type, c.mask_pow, thr, ctx->d_lens, ctx->T, ctx->F, K);
+                ew_launch(k_mask_rows, nTF, st, (const c32*)zy, (const float*)mc, (c32*)rows_s, (c32*)rows_n, nTF);
                 Zs_rows = rows_s;
                 Zn_rows = rows_n;
             } break;
             case DISCO_MZ_ORACLE_REFS:
-                hipLaunchKernelGGL(k_pick_channel, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)Xs, (c32*)rows_s, nTF, M, c.ref_mic);
-                hipLaunchKernelGGL(k_pick_channel, dim3(ew_grid(nTF)), dim3(256), 0, st, (const c32*)Xn, (c32*)rows_n, nTF, M, c.ref_mic);
+                ew_launch(k_pick_channel, nTF, st, (const c32*)Xs, (c32*)rows_s, nTF, M, c.ref_mic);
+                ew_launch(k_pick_channel, nTF, st, (const c32*)Xn, (c32*)rows_n, nTF, M, c.ref_mic);
                 Zs_rows = rows_s;
                 Zn_rows = rows_n;
                 break;
@@ -505,14 +484,10 @@ extern "C" int disco_tango_reference(disco_ctx* ctx, const float* y, const float
 
 static void iterated_steps(disco_ctx* ctx, const PathArgs& a, int iters, Steps& st) {
     const disco_cfg& c = ctx->cfg;
-    const WsLayout l = ws_layout(ctx);
     const float *y = a.y, *mask_z = a.mask_z, *mask_w = a.mask_w;
     float* out = a.out;
-    disco_c32* X = (disco_c32*)(a.ws + l.X);
-    disco_c32* z = a.z_y ? a.z_y : (disco_c32*)(a.ws + l.z);
-    disco_c32* yo = a.yf ? a.yf : (disco_c32*)(a.ws + l.yf);
-    disco_c32* w_loc = (disco_c32*)(a.ws + l.w);
-    disco_c32* w_glo = (disco_c32*)(a.ws + l.w2);
+    const PathBufs b = path_bufs(ctx, a);
+    disco_c32 *X = b.X, *z = b.z, *yo = b.yo, *w_loc = b.w, *w_glo = b.w2;
     const int64_t G = (int64_t)c.rooms * c.nodes;
     const int M = c.mics, P2 = c.mics + c.nodes - 1;
     const bool same_mask = mask_w == mask_z;

@@ -28,10 +28,9 @@ int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, con
     const int M = c.mics, K = c.nodes, P = M + K - 1;
     if (!w_loc || !z || !room_cov_ok(ctx, X, mask)) return fail(ctx, DISCO_E_ARG, "room covariance: shape / state does not qualify");
     const int chunks = room_chunks(ctx);
-    const long long G = (long long)c.rooms * K;
-    const int NP = P * (P + 1) / 2;
+    const SumsPlan plan{(long long)c.rooms * K, chunks, chunks, P, true};     // the (hi, lo) pair of the one total: always the tail block
     int rc = 0;
-    float4* part = partials_begin(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4), true, &rc);
+    float4* part = partials_begin(ctx, plan, &rc);
     if (rc) return rc;
     RoomArgs a;
     a.X = (const c32*)X;
@@ -56,7 +55,7 @@ int room_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, con
         if (items >= 64) nwg = std::max(64u, nwg / 64 * 64);
         if (!launch_room_s8(M, K, nwg, (hipStream_t)s, a)) return fail(ctx, DISCO_E_UNSUPPORTED, "room covariance: shape not instantiated");
     }
-    partials_commit(ctx, chunks, P, true);
+    partials_commit(ctx, plan);
     return check_launch(ctx, "k_room_cov");
 }
 }  // namespace disco_host

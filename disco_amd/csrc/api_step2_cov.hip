@@ -28,11 +28,9 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
     const bool skiploc = lead == LeadBlock::Step1, packed = layout == XLayout::Packed;
     const int tiles = (ctx->F - 1) / 64;
     const int chunks = step2_chunks(ctx, tiles + 1);
-    const long long G = (long long)c.rooms * K;
-    const int NP = P * (P + 1) / 2;
-    const size_t need = (size_t)G * chunks * ctx->F * NP * sizeof(float4);
+    const SumsPlan plan{(long long)c.rooms * K, chunks, chunks, P, skiploc};
     int rc = 0;
-    float4* part = partials_begin(ctx, need, skiploc, &rc);
+    float4* part = partials_begin(ctx, plan, &rc);
     if (rc) return rc;
     const Step2Args a = step2_args(ctx, X, mask_w, w_loc, nullptr, z_out, nullptr, part, chunks);
     const long long nblk = (long long)c.rooms * (tiles + 1) * chunks;
@@ -45,7 +43,7 @@ int step2_cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask_w, 
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_step2_cov_fused<M_, K_, SKIPLOC, PACK>), dim3((unsigned)nblk), dim3(64 * K_), 0, (hipStream_t)s, a);
     }); }); });
     if (!found) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_step2_cov_fused: unsupported (M, K) combination");
-    partials_commit(ctx, chunks, P, skiploc);
+    partials_commit(ctx, plan);
     return check_launch(ctx, "k_step2_cov_fused");
 }
 
@@ -63,24 +61,19 @@ extern "C" int disco_step2_cov_fused_reuse(disco_ctx* ctx, const disco_c32* X, c
 extern "C" int disco_step2_cov_fused(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
                                      disco_c32* z_out, disco_c32* Rss, disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
-    if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_step2_cov_fused: Rss and Rnn must both be given or both be NULL");
-    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Accumulate, XLayout::Public);
-    if (rc || !Rss) return rc;
-    return cov_finalize(ctx, Rss, Rnn, s);
+    return cov_pass_entry(ctx, "disco_step2_cov_fused", Rss, Rnn, s,
+                          [&] { return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Accumulate, XLayout::Public); });
 }
 
 // test-only: the same passes reading X in the packed workspace layout (include/disco_hip.h)
 extern "C" int disco_selftest_step2_cov_packed(disco_ctx* ctx, const disco_c32* X, const float* mask_w, const disco_c32* w_loc,
                                                disco_c32* z_out, disco_c32* Rss, disco_c32* Rnn, int reuse, disco_stream s) {
     DISCO_ENTER(ctx);
-    if ((Rss == nullptr) != (Rnn == nullptr) || (reuse && Rss))
-        return fail(ctx, DISCO_E_ARG, "disco_selftest_step2_cov_packed: Rss and Rnn must both be given or both be NULL, and NULL with reuse");
-    if (reuse) {
-        if (!step1_any(ctx) || ctx->cfg.nodes < 2 || ctx->Kl != ctx->cfg.nodes || !step1_held(ctx, X, mask_w))
+    const char* refusal = "disco_selftest_step2_cov_packed: Rss and Rnn must both be given or both be NULL, and NULL with reuse";
+    if (reuse && (Rss || Rnn)) return fail(ctx, DISCO_E_ARG, refusal);
+    return cov_pass_entry(ctx, "disco_selftest_step2_cov_packed", Rss, Rnn, s, [&] {
+        if (reuse && (!step1_any(ctx) || ctx->cfg.nodes < 2 || ctx->Kl != ctx->cfg.nodes || !step1_held(ctx, X, mask_w)))
             return fail(ctx, DISCO_E_ARG, "disco_selftest_step2_cov_packed: no step-1 partial sums of X / mask_w are held by this context");
-        return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Step1, XLayout::Packed);
-    }
-    int rc = step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, LeadBlock::Accumulate, XLayout::Packed);
-    if (rc || !Rss) return rc;
-    return cov_finalize(ctx, Rss, Rnn, s);
+        return step2_cov_partials(ctx, X, mask_w, w_loc, z_out, s, reuse ? LeadBlock::Step1 : LeadBlock::Accumulate, XLayout::Packed);
+    }, refusal);
 }

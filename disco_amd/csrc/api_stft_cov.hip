@@ -44,12 +44,12 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
         if (rc0) return rc0;
         return STAGE(ctx, s, "cov1", cov_partials(ctx, X, mask_z, nullptr, nullptr, 0, M, s));
     }
-    const long long G = (long long)c.rooms * ctx->Kl;
     int runw = 0;
     const int chunks = stft_cov_chunks(ctx, &runw);
-    const int NP = M * (M + 1) / 2;
+    const SumsPlan plan{(long long)c.rooms * ctx->Kl, chunks, chunks, M, false};
+    const long long G = plan.G;
     int rc = 0;
-    float4* part = partials_begin(ctx, (size_t)G * chunks * ctx->F * NP * sizeof(float4), false, &rc);
+    float4* part = partials_begin(ctx, plan, &rc);
     if (rc) return rc;
     if (G * chunks > 0x7fffffffLL) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: batch too large");
     const auto launch = [&](auto n512, auto st, auto pack) {
@@ -70,7 +70,7 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
         return with_bool(store, [&](auto st) { return with_bool(packed, [&](auto pack) { return launch(n512, st, pack); }); });
     }));
     if (!ok) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_stft_cov_fused: unsupported mic count");
-    partials_commit(ctx, chunks, M, false);
+    partials_commit(ctx, plan);
     // kept for a possible re-use by step 2, unless there is nothing to pair these sums with later (no spectra; a shard runs the staged step 2)
     if (store && !sharded(ctx)) step1_keep(ctx, X, mask_z);
     return check_launch(ctx, "k_stft_cov");
@@ -81,20 +81,14 @@ int stft_cov_partials(disco_ctx* ctx, const float* y, const float* mask_z, disco
 extern "C" int disco_stft_cov_fused(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_c32* Rss,
                                     disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
-    if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_stft_cov_fused: Rss and Rnn must both be given or both be NULL");
-    int rc = stft_cov_partials(ctx, y, mask_z, X, s);
-    if (rc || !Rss) return rc;
-    return cov_finalize(ctx, Rss, Rnn, s);
+    return cov_pass_entry(ctx, "disco_stft_cov_fused", Rss, Rnn, s, [&] { return stft_cov_partials(ctx, y, mask_z, X, s); });
 }
 
 // test-only: the same pass writing X in the packed workspace layout (include/disco_hip.h)
 extern "C" int disco_selftest_stft_cov_packed(disco_ctx* ctx, const float* y, const float* mask_z, disco_c32* X, disco_c32* Rss,
                                               disco_c32* Rnn, disco_stream s) {
     DISCO_ENTER(ctx);
-    if ((Rss == nullptr) != (Rnn == nullptr)) return fail(ctx, DISCO_E_ARG, "disco_selftest_stft_cov_packed: Rss and Rnn must both be given or both be NULL");
     StftCovOpts o;
     o.layout = XLayout::Packed;
-    int rc = stft_cov_partials(ctx, y, mask_z, X, s, o);
-    if (rc || !Rss) return rc;
-    return cov_finalize(ctx, Rss, Rnn, s);
+    return cov_pass_entry(ctx, "disco_selftest_stft_cov_packed", Rss, Rnn, s, [&] { return stft_cov_partials(ctx, y, mask_z, X, s, o); });
 }

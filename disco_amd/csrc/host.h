@@ -213,8 +213,33 @@ static inline bool has_lengths(const disco_ctx* ctx) { return ctx->d_lens != nul
 // whole-path entry points work on all nodes of a room and on their own plain [R][K] exchanged-signal arrays
 static inline bool sharded(const disco_ctx* ctx) { return ctx->Kl != ctx->cfg.nodes || ctx->zblk != ctx->cfg.nodes; }
 
+// ---- the family: a context and its half-batch children ------------------------------------------------------------------------------
+// Every walk over "this context and its children" goes through these two (the parent first), and what a child takes from its parent is
+// stated once, in child_follow (api_core.hip).
+template <class Ctx, class Fn>
+inline void for_children(Ctx* ctx, Fn fn) {                // fn(child, h) for each child that exists
+    for (int h = 0; h < 2; ++h)
+        if (ctx->half[h]) fn(ctx->half[h], h);
+}
+template <class Ctx, class Fn>
+inline void for_family(Ctx* ctx, Fn fn) {                  // fn(context): the parent, then its children
+    fn(ctx);
+    for_children(ctx, [&](auto* ch, int) { fn(ch); });
+}
+// first room of child h in its parent's batch: the rooms are split [0, R / 2) and [R / 2, R)
+static inline int child_room0(const disco_ctx* parent, int h) { return h ? parent->cfg.rooms / 2 : 0; }
+// a child's failure reported as the parent's: its message lifted, its code returned
+static inline int lift_child_error(disco_ctx* ctx, const disco_ctx* child, int rc) { return fail(ctx, rc, child->err); }
+
 namespace disco_host {
 using disco::c32;
+// the pieces of per-context state a child follows its parent in (child_follow)
+enum { FOLLOW_TUNING = 1, FOLLOW_OPTIONS = 2, FOLLOW_STAGES = 4, FOLLOW_LENGTHS = 8, FOLLOW_ALL = 15 };
+// child h takes the pieces `what` from its parent and drops what each invalidates (the definition says which)
+void child_follow(const disco_ctx* parent, int h, int what);
+// reserve_scratch for the context, then for its children
+int reserve_family(disco_ctx* ctx);
+
 struct WsLayout {
     size_t X, z, yf, Rss, Rnn, w, w2, total;
 };
@@ -222,7 +247,21 @@ struct RefLayout {
     size_t Xy, Xs, Xn, zy, zs, zn_, znres, rows_s, rows_n, mz, mw, mc, Rss, Rnn, Rtmp, w_loc, w_glo, total;
 };
 inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+// offsets of consecutive aligned arrays in a workspace: take(bytes) -> where the array starts; `o`: the total so far
+struct Take {
+    size_t o = 0;
+    size_t operator()(size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes);
+        return at;
+    }
+};
 inline unsigned ew_grid(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, 16384); }
+// an element-wise kernel over n items: 256 threads per workgroup, grid-stride beyond 16384 workgroups
+template <class Kernel, class... Args>
+inline void ew_launch(Kernel k, long long n, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(k, dim3(ew_grid(n)), dim3(256), 0, st, args...);
+}
 WsLayout ws_layout(const disco_ctx* ctx);
 RefLayout ref_layout(const disco_ctx* ctx);
 
@@ -238,10 +277,22 @@ int grow(disco_ctx* ctx, DevBlock& b, size_t need);       // no-op when large en
 int ensure_own_ws(disco_ctx* ctx, size_t bytes);          // ... of own_ws; a steps = 1 state of disco_tango_reference goes with the freed block
 int reserve_scratch(disco_ctx* ctx);
 // the partial sums (struct Partials above)
-// a producer, before its launch: the block it writes (tail: the tail block), `bytes` large; NULL with *rc set when that fails
-float4* partials_begin(disco_ctx* ctx, size_t bytes, bool tail, int* rc);
+// What one covariance pass leaves: for each of G nodes and each bin, `blocks` blocks of P (P + 1) / 2 float4, in the full or the tail block.
+// A producer builds its plan once, before its launch; the block is sized (partials_begin) and the record written (partials_commit) from
+// that one value, and bytes() is the only place the size of such sums is written.
+struct SumsPlan {
+    long long G;         // nodes of the batch held by this context: rooms x Kl
+    int chunks;          // frame chunks of the launch
+    int blocks;          // blocks per node and bin: `chunks`, or two per chunk where the kernel hands over (hi, lo) pairs
+    int P;
+    bool tail;
+    int pairs() const { return P * (P + 1) / 2; }
+    size_t bytes(int F) const { return (size_t)G * blocks * F * pairs() * sizeof(float4); }
+};
+// a producer, before its launch: the block its plan names, large enough for it; NULL with *rc set when that fails
+float4* partials_begin(disco_ctx* ctx, const SumsPlan& plan, int* rc);
 // ... after it: what it left.  Sums in the full block end the kept step-1 record; a step-1 producer re-establishes it with step1_keep
-void partials_commit(disco_ctx* ctx, int blocks, int P, bool tail);
+void partials_commit(disco_ctx* ctx, const SumsPlan& plan);
 void step1_keep(disco_ctx* ctx, const void* X, const void* mask);     // the sums just committed are step-1 sums of X with mask
 bool step1_any(const disco_ctx* ctx);                                 // step-1 sums of this context's M are kept
 bool step1_held(const disco_ctx* ctx, const void* X, const void* mask);   // ... and were computed from THESE arrays: the re-use guard
@@ -261,6 +312,9 @@ bool partials_pending(const disco_ctx* ctx, PendingSums* out);
 // half-batch children of the overlapped whole-path calls: created when the batch is large enough (or the option forces it)
 int ensure_halves(disco_ctx* ctx);
 bool overlap_applies(const disco_ctx* ctx);
+// the workspace of a whole-path call: the caller's if given (size-checked), else the context's own (grown on demand)
+int locate_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, size_t need, char** ws_out, const char* who);
+// ... for a call that overwrites it: a steps = 1 state of disco_tango_reference kept in that workspace ends here
 int acquire_ws(disco_ctx* ctx, void* workspace, size_t workspace_bytes, const WsLayout& l, char** ws_out, const char* who);
 
 // transforms of signals of any length with the context's window / FFT size / padding (api_stft.hip)
@@ -274,6 +328,17 @@ int lengths_sig_per_room(disco_ctx* ctx, int64_t n_sig, const char* who, int* si
 
 // stages (each leaves its partial sums pending in the context; see the definitions)
 int cov_finalize(disco_ctx* ctx, disco_c32* Rss, disco_c32* Rnn, disco_stream s);      // of the pending sums (whole triangle, full block)
+// the body of an entry point `who` that runs one covariance pass and hands out the matrices where asked: Rss and Rnn both or neither
+// (`refusal`: the message where it is not the usual one), the pass -- its sums stay pending --, cov_finalize if they were given
+template <class Pass>
+inline int cov_pass_entry(disco_ctx* ctx, const char* who, disco_c32* Rss, disco_c32* Rnn, disco_stream s, Pass pass,
+                          const char* refusal = nullptr) {
+    if ((Rss == nullptr) != (Rnn == nullptr))
+        return fail(ctx, DISCO_E_ARG, refusal ? refusal : (std::string(who) + ": Rss and Rnn must both be given or both be NULL").c_str());
+    const int rc = pass();
+    if (rc || !Rss) return rc;
+    return cov_finalize(ctx, Rss, Rnn, s);
+}
 int cov_partials(disco_ctx* ctx, const disco_c32* X, const float* mask, const disco_c32* Zs, const disco_c32* Zn, int mask_remote, int P,
                  disco_stream s, bool skiploc = false);
 bool room_cov_ok(const disco_ctx* ctx, const disco_c32* X, const float* mask);
