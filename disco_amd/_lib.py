@@ -16,6 +16,7 @@ PAD_MODES = {'reflect': 0, 'constant': 1}
 FLAG_STAGED_STEP2 = 1
 FLAG_LAZY_SCRATCH = 2
 FLAG_NO_CHILDREN = 4
+ESTOI_SEGS = 64                         # DISCO_ESTOI_SEGS of include/disco_hip.h: segments one workgroup of k_estoi_corr owns
 
 
 class DiscoCfg(C.Structure):
@@ -102,6 +103,9 @@ PROTOTYPES = {
     'disco_bss_estimates': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
     'disco_stoi_workspace_bytes': (_sz, [_vp, _i64, _i64, _int, _int, _int]),
     'disco_stoi': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
+    'disco_estoi_workspace_bytes': (_sz, [_vp, _i64, _i64, _int, _int, _int]),
+    'disco_estoi': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
+    'disco_estoi_bands': (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     'disco_reference_workspace_bytes': (_sz, [_vp]),
     'disco_tango_reference': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, C.POINTER(DiscoRefOutputs), _vp, _sz, _vp]),
     'disco_tango_enhance_iterated': (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

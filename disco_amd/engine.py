@@ -427,6 +427,46 @@ class Engine:
         under `budget_bytes` (default STOI_WORKSPACE_BUDGET; the resampled signals are about 0.72 MB per 9-s pair); the chunking does
         not change a bit of the result.  NumPy inputs are copied chunk by chunk; device-resident tensors / DevBufs are read in place.
         want_kept: also return the number of frames kept per pair, (n_pair,) int64."""
+        return self._stoi_call('disco_stoi', x, y, fs_sig, start, stop, budget_bytes, want_kept)
+
+    def estoi(self, x, y, fs_sig, start=0, stop=None, budget_bytes=None, want_kept=False):
+        """ESTOI, the extended STOI of Jensen & Taal 2016 (disco_estoi, csrc/k_estoi.h): the arguments, the chunk walk under
+        STOI_WORKSPACE_BUDGET, the status values and the returns of `stoi`.  Resampling, silent-frame removal and the 15 third-octave
+        envelopes are STOI's; every 15 x 30 segment is then normalised by rows (mean and norm over the 30 frames) and by columns (over the
+        15 bands) without clipping, and d is the mean of the column correlations, in float64.  pystoi (extended=True) adds EPS randn
+        before each normalisation so that it never divides by zero; that jitter is not reproduced (it moves d by some 1e-15 on the
+        cases of tests/estoi_checks.py): the result is deterministic, and a row or column whose centred norm is exactly 0 contributes 0."""
+        return self._stoi_call('disco_estoi', x, y, fs_sig, start, stop, budget_bytes, want_kept)
+
+    def estoi_bands(self, X, Y, frames=None):
+        """The last stage of ESTOI alone (disco_estoi_bands) on third-octave envelopes computed elsewhere: X clean, Y processed, both
+        (n_pair, 15, tmax) float32 -> (d, status), NumPy: d (n_pair,) float64, status (n_pair,) int32 -- 0 scored, 1 fewer than 30 frames
+        (d = 1e-5).  frames: None (tmax frames for every pair) or (n_pair,) integers 0 <= frames[i] <= tmax; nothing at or beyond a
+        pair's count is read.  A pair has the same bits alone and in any batch."""
+        xs, ys = tuple(int(v) for v in X.shape), tuple(int(v) for v in Y.shape)
+        if len(xs) != 3 or xs != ys or xs[1] != 15:
+            raise ValueError(f'X and Y must both be (n_pair, 15, tmax): {xs} and {ys}')
+        n_pair, _, tmax = xs
+        if min(n_pair, tmax) < 1:
+            raise ValueError(f'empty batch: {xs}')
+        pf = kf = None
+        if frames is not None:
+            fr = np.asarray(frames)
+            if fr.shape != (n_pair,) or not np.issubdtype(fr.dtype, np.integer) or np.any(fr < 0) or np.any(fr > tmax):
+                raise ValueError(f'frames must hold one integer in [0, {tmax}] per pair, shape ({n_pair},): got {fr.dtype} {fr.shape} {frames}')
+            pf, kf = self.to_device(np.ascontiguousarray(fr, dtype=np.int32), np.int32)
+        px, kx = self.to_device(X, np.float32)
+        py, ky = self.to_device(Y, np.float32)
+        n_chunk = -(-max(tmax - 29, 0) // L.ESTOI_SEGS)
+        ws = self.empty((n_pair * n_chunk + 1,), np.float64)
+        out = self.empty((n_pair, 2), np.float64)
+        st = self.empty((n_pair,), np.int32)
+        self._chk(self.lib.disco_estoi_bands(self.ctx, px, py, n_pair, tmax, pf, out.ptr, st.ptr, ws.ptr, ws.nbytes, self.stream))
+        return out.numpy()[:, 0].copy(), st.numpy()
+
+    def _stoi_call(self, name, x, y, fs_sig, start, stop, budget_bytes, want_kept):
+        """`stoi` and `estoi`: entry point `name` and its `<name>_workspace_bytes` walked over the pairs."""
+        entry, ws_bytes = getattr(self.lib, name), getattr(self.lib, name + '_workspace_bytes')
         xs, ys = tuple(int(v) for v in x.shape), tuple(int(v) for v in y.shape)
         if len(xs) != 2 or xs != ys:
             raise ValueError(f'x and y must both be (n_pair, L): {xs} and {ys}')
@@ -445,17 +485,16 @@ class Engine:
             ptaps = self._stoi_taps[p, q][0]
         n_taps = len(taps)
         step, ws = self._chunk_plan(
-            n_pair, lambda k: self.lib.disco_stoi_workspace_bytes(self.ctx, k, L, p, q, n_taps), budget_bytes, self.STOI_WORKSPACE_BUDGET,
-            lambda: self.lib.disco_stoi(self.ctx, None, None, n_pair, L, start, None, p, q, None, n_taps, None, None, None, 0, self.stream),
-            'disco_stoi')
+            n_pair, lambda k: ws_bytes(self.ctx, k, L, p, q, n_taps), budget_bytes, self.STOI_WORKSPACE_BUDGET,
+            lambda: entry(self.ctx, None, None, n_pair, L, start, None, p, q, None, n_taps, None, None, None, 0, self.stream), name)
         d = np.empty((n_pair,), np.float64)
         kept = np.empty((n_pair,), np.int64)
         status = np.empty((n_pair,), np.int32)
         for i0, n, px, py in self._chunks(n_pair, step, (x, L), (y, L)):
             out = self.empty((n, 2), np.float64)
             st = self.empty((n,), np.int32)
-            self._chk(self.lib.disco_stoi(self.ctx, px, py, n, L, start, None if pstop is None else pstop + 4 * i0, p, q, ptaps, n_taps, out.ptr,
-                                          st.ptr, ws.ptr, ws.nbytes, self.stream))
+            self._chk(entry(self.ctx, px, py, n, L, start, None if pstop is None else pstop + 4 * i0, p, q, ptaps, n_taps, out.ptr, st.ptr, ws.ptr,
+                            ws.nbytes, self.stream))
             o = out.numpy()
             d[i0:i0 + n] = o[:, 0]
             kept[i0:i0 + n] = o[:, 1].astype(np.int64)

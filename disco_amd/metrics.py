@@ -14,6 +14,8 @@ clipping / importance-weight arithmetic of the reference is applied to those.
     stoi                      pystoi.stoi as tango.py:569-578 calls it (third-party and absent here: restated from its definition with
                               pystoi's constants, csrc/k_stoi.h; pinned by the float64 yardstick of tests/stoi_checks.py, unpinned
                               against the package)
+    estoi                     the extended STOI of Jensen & Taal 2016, pystoi.stoi(..., extended=True) without its random jitter
+                              (csrc/k_estoi.h; pinned by the float64 yardstick of tests/estoi_checks.py)
     third_octave_filterbank   sigproc_utils.py:90-116
 
 `start` / `stop` select the scored span; the reference scores [fs : min_len] (tango.py:541-593), i.e. start = 16000.
@@ -218,9 +220,25 @@ def stoi(x, y, fs_sig, extended=False, start=0, stop=None):
     clipped and correlated, all on the GPU (Engine.stoi, csrc/k_stoi.h).  `start` / `stop` select the scored span; `stop` may be an
     array shaped like the leading axes, so that a batch of different clip lengths scores every pair as if it ran alone.
     Fewer than 30 frames after the removal: 1e-5 and a RuntimeWarning, as pystoi.  A span too short for a single frame (fewer than 257
-    samples at 10 kHz) raises ValueError naming the pair.  extended=True (ESTOI) is not offered."""
+    samples at 10 kHz) raises ValueError naming the pair.  extended=True raises NotImplementedError: the extended measure is `estoi`,
+    a function of its own because it leaves out the random jitter of pystoi's variant."""
     if extended:
-        raise NotImplementedError('extended STOI (ESTOI) is not offered')
+        raise NotImplementedError('extended=True is not offered here: call disco_amd.metrics.estoi (ESTOI without the random jitter of pystoi)')
+    return _stoi_family('stoi', x, y, fs_sig, start, stop)
+
+
+def estoi(x, y, fs_sig, start=0, stop=None):
+    """ESTOI, the extended STOI of Jensen & Taal 2016 (what pystoi.stoi computes with extended=True): the arguments, shapes, warning and
+    errors of `stoi`.  Resampling, silent-frame removal and the third-octave envelopes are STOI's; every 15 x 30 segment is normalised by
+    rows and then by columns, without clipping, and the column correlations are averaged, all on the GPU (Engine.estoi, csrc/k_estoi.h).
+    Restated from the definition and pinned by the float64 yardstick of tests/estoi_checks.py, unpinned against the package.  pystoi adds
+    EPS randn before each normalisation so that it never divides by zero; that jitter is not reproduced (it moves d by some 1e-15 on
+    the cases of tests/estoi_checks.py): the result is deterministic, and a row or column whose centred norm is exactly 0 contributes 0."""
+    return _stoi_family('estoi', x, y, fs_sig, start, stop)
+
+
+def _stoi_family(which, x, y, fs_sig, start, stop):
+    """`stoi` and `estoi`: Engine.<which> over the flattened leading axes, the warning and the error."""
     if isinstance(x, np.ndarray) or not hasattr(x, 'data_ptr'):
         x = np.ascontiguousarray(x, dtype=np.float32)
     if isinstance(y, np.ndarray) or not hasattr(y, 'data_ptr'):
@@ -232,7 +250,7 @@ def stoi(x, y, fs_sig, extended=False, start=0, stop=None):
     n_pair = int(np.prod(lead, dtype=np.int64))
     if stop is not None and np.ndim(stop):
         stop = np.broadcast_to(np.asarray(stop), lead).reshape(n_pair)
-    d, status = _engine().stoi(x.reshape(n_pair, L), y.reshape(n_pair, L), fs_sig, start, stop)
+    d, status = getattr(_engine(), which)(x.reshape(n_pair, L), y.reshape(n_pair, L), fs_sig, start, stop)
     if np.any(status == 2):
         i = int(np.flatnonzero(status == 2)[0])
         where = tuple(int(v) for v in np.unravel_index(i, lead)) if lead else ()

@@ -88,10 +88,14 @@ THIRD_PARTY_KEYS = ('sar_cnv', 'sir_cnv', 'sdr_cnv', 'delta_stoi_cnv', 'delta_st
                     'sdr_in_cnv', 'sir_in_cnv', 'sdr_in_dry', 'sir_in_dry', 'sar_in_dry')
 BSS_KEYS = tuple(k for k in THIRD_PARTY_KEYS if 'stoi' not in k)
 STOI_KEYS = tuple(k for k in THIRD_PARTY_KEYS if 'stoi' in k)
+# ESTOI (disco_amd.metrics.estoi) is not in the reference's pickles: its keys are added to the two dictionaries only on `estoi=True`, formed
+# as their delta_stoi* counterparts; without it the dictionaries, and so the pickles, keep the reference's key set.
+ESTOI_KEYS_TANGO = ('delta_estoi_cnv', 'delta_estoi_dry')
+ESTOI_KEYS_MWF = ('delta_estoi', 'delta_estoi_dry')
 
 
 def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
-                 bss_flen=512, stoi=False):
+                 bss_flen=512, stoi=False, estoi=False):
     """The two result dictionaries of one (room, noise) (tango.py:541-635).
     s_in, n_in (K, L): target / noise images at every node's first microphone; sf_t, nf_t (K, L): their step-2 outputs in time;
     szf_t, nzf_t (K, L): their compressed (step-1) versions in time; rnd_snrs: the drawn input SNRs; s_dry, n_dry (L,): the dry
@@ -104,7 +108,10 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
     stoi=True, with the same three signals: the STOI keys (STOI_KEYS) are filled as tango.py:569-578 fills them -- `delta_stoi_cnv` of `res`
     and `delta_stoi` of `resz` are STOI(s_in[k], sh[k]) and STOI(s_in[k], szh[k]) minus STOI(s_in[k], y[k]); with the dry sources,
     `delta_stoi_dry` of both likewise with s_dry as the clean signal.  All 6 K pairs of the room go in one Engine.stoi call.  The default
-    leaves those keys NaN."""
+    leaves those keys NaN.
+    estoi=True: `res` gains `delta_estoi_cnv` and `delta_estoi_dry`, `resz` gains `delta_estoi` and `delta_estoi_dry` (ESTOI_KEYS_TANGO,
+    ESTOI_KEYS_MWF), formed as their delta_stoi* counterparts from disco_amd.metrics.estoi on the same pairs; NaN without the three time
+    signals (the `_dry` ones without the dry sources).  The default adds no key."""
     from .. import metrics as dm
     K = np.shape(s_in)[0]
     bss = y_in is not None and sh_t is not None and szh_t is not None
@@ -154,16 +161,21 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
             res['sdr_in_dry'] = resz['sdr_in_dry'] = sdr[:, 2]
             res['sir_in_dry'] = resz['sir_in_dry'] = sir[:, 2]
             res['sar_in_dry'] = resz['sar_in_dry'] = sar[:, 2]
-    if stoi and bss:
+    if estoi:
+        for r, keys in ((res, ESTOI_KEYS_TANGO), (resz, ESTOI_KEYS_MWF)):
+            r.update({k: nan.copy() for k in keys})
+    measures = [(nm, f) for nm, f, on in (('stoi', dm.stoi, stoi), ('estoi', dm.estoi, estoi)) if on and bss]
+    if measures:                                                                           # the pairs are stacked once for both measures
         clean = [cut(s_in)] + ([np.repeat(cut(s_dry)[None], K, axis=0)] if s_dry is not None else [])
         proc = np.stack([cut(y_in), cut(sh_t), cut(szh_t)])                                # (3, K, L'): in, out, out_z
         x = np.stack([np.broadcast_to(c, proc.shape) for c in clean])                      # (1 or 2, 3, K, L')
-        d = np.asarray(dm.stoi(x, np.broadcast_to(proc, x.shape), fs))                     # tango.py:569-574
-        res['delta_stoi_cnv'] = d[0, 1] - d[0, 0]                                          # :575
-        resz['delta_stoi'] = d[0, 2] - d[0, 0]                                             # :577
+    for name, measure in measures:
+        d = np.asarray(measure(x, np.broadcast_to(proc, x.shape), fs))                     # tango.py:569-574
+        res[f'delta_{name}_cnv'] = d[0, 1] - d[0, 0]                                       # :575
+        resz[f'delta_{name}'] = d[0, 2] - d[0, 0]                                          # :577
         if s_dry is not None:
-            res['delta_stoi_dry'] = d[1, 1] - d[1, 0]                                      # :576
-            resz['delta_stoi_dry'] = d[1, 2] - d[1, 0]                                     # :578
+            res[f'delta_{name}_dry'] = d[1, 1] - d[1, 0]                                   # :576
+            resz[f'delta_{name}_dry'] = d[1, 2] - d[1, 0]                                  # :578
     return res, resz
 
 
@@ -199,7 +211,7 @@ def _trim(a, L):
 
 
 def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
-                  bss_flen=512, stoi=False, lengths=None):
+                  bss_flen=512, stoi=False, lengths=None, estoi=False):
     """`room_results` for a whole batch of rooms, clips of different lengths included, in a handful of launches instead of one pass of
     Python per room: signals (R, K, L), dry sources (R, L), rnd_snrs (R, ...), as NumPy arrays (copied to the device) or -- all of them --
     device-resident torch tensors (read in place; no signal comes to the host).  lengths (R,): room r is scored over [fs, lengths[r]),
@@ -210,7 +222,8 @@ def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_
     The band levels of a dry source are computed once per room.  The BSS part walks whole rooms in chunks whose workspace stays under
     Engine.BSS_WORKSPACE_BUDGET: a chunk's estimate sets are formed on the device (Engine.bss_estimates, 24 L bytes per node) and scored
     twice, against (s_in, n_in) per node and against the room's dry pair with 3 K estimate sets.  An all-zero reference raises
-    ValueError naming the room and the node.  STOI: one Engine.stoi call for all 6 R K pairs, with a stop per pair."""
+    ValueError naming the room and the node.  STOI: one Engine.stoi call for all 6 R K pairs, with a stop per pair; estoi=True: the
+    four ESTOI keys of `room_results` from one Engine.estoi call on the same pairs and stops."""
     from .. import metrics as dm
     R, K = (int(v) for v in np.shape(s_in)[:2])
     bss = y_in is not None and sh_t is not None and szh_t is not None
@@ -312,7 +325,11 @@ def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_
             res['sdr_in_dry'] = resz['sdr_in_dry'] = sdr[..., 2]
             res['sir_in_dry'] = resz['sir_in_dry'] = sir[..., 2]
             res['sar_in_dry'] = resz['sar_in_dry'] = sar[..., 2]
-    if stoi and bss:
+    if estoi:
+        for r, keys in ((res, ESTOI_KEYS_TANGO), (resz, ESTOI_KEYS_MWF)):
+            r.update({k: nan.copy() for k in keys})
+    measures = [(nm, f) for nm, f, on in (('stoi', eng.stoi, stoi), ('estoi', eng.estoi, estoi)) if on and bss]
+    if measures:                                                                          # the pairs are stacked once for both measures
         Ls = Lr
         flat = lambda a: _trim(a, Ls).reshape(R * K, Ls)
         clean = [flat(sig['s_in'])]
@@ -323,7 +340,8 @@ def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_
         proc = [flat(sig[nm]) for nm in ('y_in', 'sh_t', 'szh_t')]                        # in, out, out_z
         x = cat([c for c in clean for _ in proc])                                         # (6 R K or 3 R K, Ls): [clean][proc][room][node]
         yy = cat([p for _ in clean for p in proc])
-        d, status = eng.stoi(x, yy, fs, fs, np.tile(stop_rk, len(clean) * 3))             # tango.py:569-574
+    for name, measure in measures:
+        d, status = measure(x, yy, fs, fs, np.tile(stop_rk, len(clean) * 3))              # tango.py:569-574
         if np.any(status == 2):
             i = int(np.flatnonzero(status == 2)[0]) % (R * K)
             raise ValueError(f'room {i // K}, node {i % K}: the scored span is too short for one frame (fewer than 257 samples at 10 kHz)')
@@ -332,11 +350,11 @@ def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_
             warnings.warn('Not enough STFT frames to compute intermediate intelligibility measure after removing silent frames. '
                           'Returning 1e-5. Please check you wav files', RuntimeWarning)
         d = d.reshape(len(clean), 3, R, K)
-        res['delta_stoi_cnv'] = d[0, 1] - d[0, 0]                                         # :575
-        resz['delta_stoi'] = d[0, 2] - d[0, 0]                                            # :577
+        res[f'delta_{name}_cnv'] = d[0, 1] - d[0, 0]                                      # :575
+        resz[f'delta_{name}'] = d[0, 2] - d[0, 0]                                         # :577
         if dry:
-            res['delta_stoi_dry'] = d[1, 1] - d[1, 0]                                     # :576
-            resz['delta_stoi_dry'] = d[1, 2] - d[1, 0]                                    # :578
+            res[f'delta_{name}_dry'] = d[1, 1] - d[1, 0]                                  # :576
+            resz[f'delta_{name}_dry'] = d[1, 2] - d[1, 0]                                 # :578
     return res, resz
 
 

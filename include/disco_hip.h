@@ -125,7 +125,7 @@ int  disco_set_z_blocks(disco_ctx* ctx, int nodes_per_block);
  * length = lengths[r], with T_r = 1 + lengths[r] / hop frames:
  *   - samples at and beyond lengths[r] are never read (they may hold anything, NaN included): the transform reflects or zero-pads at
  *     lengths[r].  The metrics honour the same promise through a stop per signal: disco_pair_stats_spans, disco_band_stats_spans,
- *     disco_lag_corr_spans, disco_bss_eval_spans, disco_bss_estimates and disco_stoi read nothing at or beyond a signal's stop;
+ *     disco_lag_corr_spans, disco_bss_eval_spans, disco_bss_estimates, disco_stoi and disco_estoi read nothing at or beyond a signal's stop;
  *   - frames t >= T_r do not exist: they enter no statistic; spectra, z, yf and the masks the library computes are exact zeros there.
  *     Masks the CALLER passes in must be FINITE in those frames (their values do not matter);
  *   - output samples n < lengths[r] are the inverse transform with the window sum of T_r frames, n >= lengths[r] exact zeros;
@@ -606,8 +606,8 @@ int disco_bss_estimates(disco_ctx* ctx, const float* y, const float* sh, const f
                         const int32_t* stop, float* ests, disco_stream s);
 
 /* ---- STOI (what tango.py:569-578 takes from pystoi.stoi) ------------------------------------------------------------
- * Restated from its definition (Taal, Hendriks, Heusdens, Jensen 2011) with pystoi's constants and conventions; not extended
- * (ESTOI).  x [n_pair][len] clean, y [n_pair][len] processed, float; pair i is scored over [start, stop[i]) (stop: device array
+ * Restated from its definition (Taal, Hendriks, Heusdens, Jensen 2011) with pystoi's constants and conventions; the extended
+ * measure is disco_estoi below.  x [n_pair][len] clean, y [n_pair][len] processed, float; pair i is scored over [start, stop[i]) (stop: device array
  * of n_pair int32, clamped into [start, len]; NULL = len for every pair).  p / q = 10000 / fs_sig in lowest terms; p == q: the
  * signals are at 10 kHz already and taps is not read.  Otherwise taps [n_taps] float64 (device memory, n_taps = 2 L + 1 odd, at
  * most 65536 -- DISCO_E_UNSUPPORTED beyond) is the normalised anti-aliasing filter h of pystoi's resample_oct and both signals
@@ -624,6 +624,29 @@ int disco_bss_estimates(disco_ctx* ctx, const float* y, const float* sh, const f
 size_t disco_stoi_workspace_bytes(const disco_ctx* ctx, int64_t n_pair, int64_t len, int p, int q, int n_taps);
 int disco_stoi(disco_ctx* ctx, const float* x, const float* y, int64_t n_pair, int64_t len, int start, const int32_t* stop, int p, int q,
                const double* taps, int n_taps, double* out, int32_t* status, void* workspace, size_t workspace_bytes, disco_stream s);
+
+/* ---- ESTOI (extended STOI: Jensen, Taal 2016; what pystoi computes with extended=True) -------------------------------
+ * The arguments, the resampling, the kept frames, the 15 third-octave envelopes X, Y (15 x T), out[i][2], the status values, the
+ * refusals and their codes are those of disco_stoi; the last stage differs.  With J = T - 29 segments and Xm = X[:, m : m + 30], Ym
+ * alike, in float64: every row of Xm, Ym minus its mean over the 30 frames, divided by (its norm + EPS); every column of the
+ * row-normalised matrices minus its mean over the 15 bands, divided by (its norm + EPS); d_m = sum(Xn o Yn) / 30; d = sum_m d_m / J.
+ * EPS = 2.220446049250313e-16.  No clipping.  Restated from the definition, as STOI is.  pystoi adds EPS randn to the matrices
+ * before each normalisation so that it never divides by zero; that jitter is NOT reproduced (it moves d by some 1e-15): the result
+ * is deterministic and a row or column whose centred norm is exactly 0 contributes 0.  An all-zero x gives d = 0.  A pair's result
+ * is bit-identical from run to run and whatever else is in the batch (no atomics).
+ * workspace: at least disco_estoi_workspace_bytes(ctx, n_pair, len, p, q, n_taps); 0 for a shape disco_estoi refuses. */
+#define DISCO_ESTOI_SEGS 64 /* segments of 30 frames one workgroup of the last stage owns */
+size_t disco_estoi_workspace_bytes(const disco_ctx* ctx, int64_t n_pair, int64_t len, int p, int q, int n_taps);
+int disco_estoi(disco_ctx* ctx, const float* x, const float* y, int64_t n_pair, int64_t len, int start, const int32_t* stop, int p, int q,
+                const double* taps, int n_taps, double* out, int32_t* status, void* workspace, size_t workspace_bytes, disco_stream s);
+/* disco_estoi_bands: the last stage of ESTOI alone, on envelopes computed elsewhere.  tob_x, tob_y [n_pair][15][tmax] float (device
+ * memory; clean, processed); frames: device array of n_pair int32, pair i has T = frames[i] frames, clamped into [0, tmax]; NULL =
+ * tmax for every pair.  Nothing at or beyond a pair's T is read.  out[i][2] = { d, T };  status[i]: 0 scored; 1 T < 30, d = 1e-5.
+ * A NaN in a pair's envelopes makes that pair's d NaN and touches no other pair.  The bits of a pair are those disco_estoi gives for
+ * the same envelopes, alone or in any batch.  workspace: at least 8 n_pair ceil(max(tmax - 29, 0) / DISCO_ESTOI_SEGS) bytes (one
+ * partial sum per workgroup); may be NULL when that is 0. */
+int disco_estoi_bands(disco_ctx* ctx, const float* tob_x, const float* tob_y, int64_t n_pair, int tmax, const int32_t* frames, double* out,
+                      int32_t* status, void* workspace, size_t workspace_bytes, disco_stream s);
 
 /* ---- the step before the path: reverberation of dry signals ------------------------------------
  * out[i][c][0:out_len] = np.convolve(dry[i], rir[i][c])[:out_len]  (zero beyond dry_len + rir_len - 1), the operation of

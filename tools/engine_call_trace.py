@@ -11,7 +11,8 @@ DevBuf / CPU-torch inputs, optional outputs, `out=`, aliased arguments, the thre
 
 Two trees agree when their normalised traces are identical call for call apart from the positions of the `disco_dev_free` calls (when
 Python drops a buffer is not part of the contract; that no call receives a pointer into a freed allocation is, and is asserted), and when
-the exceptions the script provokes are identical in type and message.
+the exceptions the script provokes are identical in type and message.  Methods that only one of the two trees has (a change that adds one)
+are scripted in a marked section at the end, which is then left out of the comparison: everything before it lines up allocation for allocation.
 """
 import argparse
 import bisect
@@ -166,7 +167,7 @@ class RecordingLib:
     def _bss_workspace_bytes(self, name, args, entry):
         return self.per_item * int(args[1])
 
-    _stoi_workspace_bytes = _bss_workspace_bytes
+    _stoi_workspace_bytes = _estoi_workspace_bytes = _bss_workspace_bytes
 
     def _lag_corr_workspace_bytes(self, name, args, entry):
         return 64
@@ -201,7 +202,7 @@ def run_script(engine, lib):
     Engine = engine.Engine
     eng = Engine(rooms=R, nodes=K, mics=M, length=LS, n_fft=16, lib=lib)
     T, F = eng.T, eng.F
-    errors, covered, counter = [], set(), [0]
+    errors, covered, counter, absent = [], set(), [0], set()
 
     def mk(kind, shape, dtype=np.float32, fill=None):
         counter[0] += 1
@@ -229,6 +230,9 @@ def run_script(engine, lib):
     def call(name, *a, _on=None, **kw):
         """One step: the method's name goes into the trace, so that the two traces line up; what it raises is recorded, not raised."""
         on = eng if _on is None else _on
+        if not hasattr(on, name):                                       # a method this tree does not have (yet): nothing is recorded, and the
+            absent.add(name)                                            # comparison leaves the other tree's steps of that name out
+            return None
         covered.add(('push' if name == 'push' else name))
         lib.trace.append(['step', name])
         try:
@@ -443,6 +447,37 @@ def run_script(engine, lib):
     lib.returns['disco_reserve'] = -1
     call('reserve')
     del lib.returns['disco_reserve']
+    # Methods newer than the first trees this script compared go last: every allocation number before this point is then the same in a
+    # parent that lacks them and in a change that has them.  The section is marked: when one tree lacks a method of it, the comparison leaves
+    # the section out of both traces (`comparable`), and the change's own trace of it still answers for its pointers and its leaks.
+    lib.trace.append(['section', 'newer methods'])
+    for kind in KINDS:
+        mkf = lambda *shape: mk(kind, shape, np.float32)
+        n = 5
+        a, b = mkf(n, LS), mkf(n, LS)
+        for stop in (None, 50, np.array([10, 20, 30, 40, 64]), np.array([10, 20, 30]), 65):
+            call('estoi', a, b, 16000, start=5, stop=stop)
+            call('estoi', a, b, 10000, start=5, stop=stop, budget_bytes=2000, want_kept=True)
+        call('estoi', a, mkf(n, LS - 1), 16000)
+        call('estoi', mk('dev' if kind == 'np' else 'np', (n, LS)), b, 8000, budget_bytes=2999, stop=np.array([10, 20, 30, 40, 64]))
+        lib.per_item = 0
+        call('estoi', a, b, 16000, stop=40)
+        lib.per_item = 1000
+        lib.returns['disco_estoi'] = -2
+        call('estoi', a, b, 16000)
+        lib.returns.clear()
+        X, Y = mkf(3, 15, 100), mkf(3, 15, 100)
+        call('estoi_bands', X, Y)
+        call('estoi_bands', X, Y, frames=np.array([29, 30, 100]))
+        call('estoi_bands', X, Y, frames=np.array([29, 30, 101]))
+        call('estoi_bands', X, Y, frames=np.array([29., 30., 40.]))
+        call('estoi_bands', X, mkf(3, 15, 99))
+        call('estoi_bands', mkf(3, 14, 100), mkf(3, 14, 100))
+        lib.returns['disco_estoi_bands'] = -1
+        call('estoi_bands', X, Y)
+        lib.returns.clear()
+        del a, b, X, Y
+    lib.trace.append(['section', 'end'])
     # every temporary is gone once the results are: what is live now belongs to the engine's cache of resampling taps
     gc.collect()
     cached = {lib._alloc_of(v[1].ptr) for v in getattr(eng, '_stoi_taps', {}).values()}
@@ -457,15 +492,16 @@ def run_script(engine, lib):
     lib.returns.clear()
     public = {nm for nm in vars(Engine) if not nm.startswith('_') and (callable(getattr(Engine, nm)) or isinstance(getattr(Engine, nm), property))}
     missing = sorted(public - covered)
-    return errors, sorted(covered), missing, leaked
+    return errors, sorted(covered), missing, leaked, sorted(absent)
 
 
 def dump(tree):
     engine, _lib = load_engine(tree)
     lib = RecordingLib(_lib.PROTOTYPES)
-    errors, covered, missing, leaked = run_script(engine, lib)
+    errors, covered, missing, leaked, absent = run_script(engine, lib)
     late = [f for f in lib.frees if f[2] is not None and f[2] >= f[1]]
-    return dict(trace=lib.trace, errors=errors, covered=covered, missing=missing, leaked=leaked, violations=lib.violations + [f'free {f}' for f in late],
+    return dict(trace=lib.trace, errors=errors, covered=covered, missing=missing, leaked=leaked, absent=absent,
+                violations=lib.violations + [f'free {f}' for f in late],
                 allocations=len(lib.starts), frees=len(lib.frees), engine_lines=len(open(engine.__file__).read().splitlines()))
 
 
@@ -497,6 +533,17 @@ def without_frees(trace):
     return [e for e in trace if e[0] != 'disco_dev_free']
 
 
+def without_section(trace):
+    """The trace without what lies between the markers of the section of newer methods."""
+    out, skip = [], False
+    for e in trace:
+        if e[0] == 'section':
+            skip = e[1] != 'end'
+        elif not skip:
+            out.append(e)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('trees', nargs='*', help='PARENT_TREE CHANGE_TREE')
@@ -526,14 +573,22 @@ def main():
         return 0 if mc - mp <= spread else 1
     p, c = child('--dump', parent), child('--dump', change)
     tp, tc = without_frees(p['trace']), without_frees(c['trace'])
+    one_sided = sorted(set(p['absent']) ^ set(c['absent']))               # methods only one tree has: their section is left out of both
+    ep, ec = p['errors'], c['errors']
+    if one_sided:
+        tp, tc = without_section(tp), without_section(tc)
+        ep, ec = ([e[1:] for e in errs if e[1] not in one_sided] for errs in (ep, ec))       # positions shift with the section: names and messages in order
     lines = []
     first = next((i for i, (x, y) in enumerate(zip(tp, tc)) if x != y), None if len(tp) == len(tc) else min(len(tp), len(tc)))
-    same_errors = p['errors'] == c['errors']
+    same_errors = ep == ec
     ok = first is None and same_errors and not c['violations'] and not c['leaked'] and not c['missing'] and not p['violations']
     lines.append('engine call trace: parent and change ' + ('IDENTICAL' if first is None and same_errors else 'DIFFER') +
                  ' (normalised traces call for call, the positions of disco_dev_free apart; raised exceptions by type and message)')
     lines.append(f'calls compared: {len(tc)} entries of the change against {len(tp)} of the parent, {sum(e[0].startswith("disco_") for e in tc)} of them library calls, '
                  f'{sum(e[0] == "step" for e in tc)} scripted method calls; exceptions compared: {len(c["errors"])} against {len(p["errors"])}')
+    if one_sided:
+        lines.append(f'methods only one tree has: {", ".join(one_sided)} -- the section of newer methods is left out of both traces; the change ran it '
+                     f'({sum(e[0] == "step" for e in c["trace"]) - sum(e[0] == "step" for e in tc)} scripted calls) and its pointers and leaks are counted below')
     if first is not None:
         lines.append(f'first difference at entry {first}: parent {tp[first] if first < len(tp) else None}, change {tc[first] if first < len(tc) else None}')
         lines.append('  in step: ' + str(next((e for e in reversed(tc[:first + 1]) if e[0] == 'step'), None)))
