@@ -81,7 +81,9 @@ PROTOTYPES = {
     'disco_mask_ivad': (_int, [_vp, _vp, _i64, _vp, _vp]),
     'disco_rir_convolve': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _int, _vp]),
     'disco_ism_rir': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _f, _f, _vp, _int, _vp]),
-    'disco_gru_gates': (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    'disco_vad_samples': (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _f, _int, _vp, _vp]),
+    'disco_mix_scaled': (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp]),
+    'disco_gru_gates':(_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
     'disco_maxpool_last4': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     'disco_conv3x3_pool4': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
     'disco_crnn_features': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, C.c_float, C.c_float, _vp, _vp]),

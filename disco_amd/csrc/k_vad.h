@@ -6,6 +6,7 @@
 // One workgroup per signal.  The 0.99-quantile needs two neighbouring order statistics of ~L values: a 4-pass radix
 // select on the float bit patterns (x2 >= 0, so unsigned order = numeric order) with a 256-bin LDS histogram per pass,
 // then one pass for the next larger value.  The signal (<= 640 kB) stays in L2 across the passes.
+// The mean, the threshold and the segment counts are device functions: k_vad_samples (k_roomsynth.h) gives the same decision per sample.
 #pragma once
 #include "common.h"
 
@@ -62,13 +63,10 @@ __device__ __forceinline__ unsigned vad_select(VadShared& sh, const float* __res
     return sh.prefix;
 }
 
-static __global__ __launch_bounds__(VAD_THREADS) void k_vad_mask(const float* __restrict__ ts, float* __restrict__ mask, int L, int T,
-                                                          int F, int win, int hop, float thr_rel, float quant, int rat) {
-    __shared__ VadShared sh;
+// ---- the three phases k_vad_mask and k_vad_samples (k_roomsynth.h) share; every thread of the workgroup calls them ----------------------
+// mean of x[0..L): float64 accumulation, rounded to the float32 np.mean returns for a float32 signal
+__device__ __forceinline__ float vad_mean(VadShared& sh, const float* __restrict__ x, int L) {
     const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
-    const long long sig = blockIdx.x;
-    const float* x = ts + sig * L;
-    // ---- mean (float64 accumulation, rounded to the float32 np.mean returns for a float32 signal)
     double s = 0.0;
     for (int i = tid; i < L; i += VAD_THREADS) s += (double)x[i];
 #pragma unroll
@@ -81,8 +79,12 @@ static __global__ __launch_bounds__(VAD_THREADS) void k_vad_mask(const float* __
         sh.mean = (float)(t / (double)L);
     }
     __syncthreads();
-    const float mean = sh.mean;
-    // ---- quantile: virtual index (L-1) q, linear interpolation between the two neighbouring order statistics
+    return sh.mean;
+}
+
+// thr_rel * quantile(x2, quant): virtual index (L-1) q, linear interpolation between the two neighbouring order statistics
+__device__ __forceinline__ float vad_threshold(VadShared& sh, const float* __restrict__ x, int L, float mean, float thr_rel, float quant) {
+    const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
     const double vidx = (double)(L - 1) * (double)quant;
     const int k_lo = (int)vidx;
     const double frac = vidx - (double)k_lo;
@@ -119,8 +121,12 @@ static __global__ __launch_bounds__(VAD_THREADS) void k_vad_mask(const float* __
         sh.thr = thr_rel * q;
     }
     __syncthreads();
-    const float thr = sh.thr;
-    // ---- #(x2 > thr) per hop segment
+    return sh.thr;
+}
+
+// sh.cnt[sg] = #(x2 > thr) of hop segment sg, for the ceil(L / hop) segments (returned)
+__device__ __forceinline__ int vad_segment_counts(VadShared& sh, const float* __restrict__ x, int L, int hop, float mean, float thr) {
+    const int lane = threadIdx.x & 63, w = wave_id();
     const int n_seg = (L + hop - 1) / hop;
     for (int sg = w; sg < n_seg; sg += VAD_THREADS / 64) {
         int c = 0;
@@ -131,6 +137,18 @@ static __global__ __launch_bounds__(VAD_THREADS) void k_vad_mask(const float* __
         if (lane == 0) sh.cnt[sg] = c;
     }
     __syncthreads();
+    return n_seg;
+}
+
+static __global__ __launch_bounds__(VAD_THREADS) void k_vad_mask(const float* __restrict__ ts, float* __restrict__ mask, int L, int T,
+                                                          int F, int win, int hop, float thr_rel, float quant, int rat) {
+    __shared__ VadShared sh;
+    const int lane = threadIdx.x & 63, w = wave_id();
+    const long long sig = blockIdx.x;
+    const float* x = ts + sig * L;
+    const float mean = vad_mean(sh, x, L);
+    const float thr = vad_threshold(sh, x, L, mean, thr_rel, quant);
+    const int n_seg = vad_segment_counts(sh, x, L, hop, mean, thr);
     // ---- frame decisions + tiling over frequency.  Window n covers segments n .. n + win/hop - 1 (clipped at L).
     const int spw = win / hop;                                               // segments per window (2)
     const int n_win = (int)ceil(((double)L - (double)win) / (double)hop + 1.0);

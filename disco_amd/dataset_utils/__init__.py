@@ -1,0 +1,5 @@
+"""From dry sources to rooms the path can enhance, on the GPU (the reference's dataset_generation/gen_disco/convolve_signals.py and
+disco_theque/dataset_utils/post_generator.py, without files and without redraw loops)."""
+from .rooms import mix_rooms, simulate_rooms, snr_at_mics
+
+__all__ = ['snr_at_mics', 'simulate_rooms', 'mix_rooms']

@@ -5,7 +5,8 @@ Arrays may be given as numpy arrays (copied host->device through the library's o
 All compute happens in libdisco_hip.so; this file only marshals pointers.  No CPU fallback exists.
 The marshalling is stated once, in the helpers under "plumbing": `_out` (caller-owned or fresh output), `_alias` (a second argument that
 may be the first), `_ptr` (optional buffer -> pointer or NULL), `_span_stops` / `_span_stops_dev` (`stop` of a metric), `_chunk_plan` /
-`_chunks` (a batch walked under a workspace budget), `_pencils` (the solvers' prologue), `_selftest_pair`; each method names its dialect.
+`_chunks` (a batch walked under a workspace budget), `_pencils` (the solvers' prologue), `_selftest_pair`, `_on_host` / `_lead_stops` (the
+container rule and the `stop` over leading axes of vad_samples / mix_scaled); each method names its dialect.
 """
 import ctypes as C
 
@@ -39,10 +40,31 @@ class DevBuf:
     def reshape(self, *shape):
         v = object.__new__(DevBuf)
         v.eng, v.dtype, v.nbytes, v.ptr = self.eng, self.dtype, self.nbytes, self.ptr
-        v.shape = tuple(shape)
+        v.shape = tuple(int(s) for s in shape)
+        if v.shape.count(-1) == 1:                       # one free axis, as numpy's reshape
+            known = -int(np.prod(v.shape, dtype=np.int64))
+            v.shape = tuple(self.nbytes // self.dtype.itemsize // max(known, 1) if s == -1 else s for s in v.shape)
         v._base = self
         assert int(np.prod(v.shape, dtype=np.int64)) * v.dtype.itemsize == self.nbytes
         return v
+
+    def part(self, start, shape):
+        """A view of prod(shape) elements that begins at flat element `start`: the memory stays owned by this buffer."""
+        v = object.__new__(DevBuf)
+        v.eng, v.dtype, v.shape = self.eng, self.dtype, tuple(int(s) for s in shape)
+        v.nbytes = int(np.prod(v.shape, dtype=np.int64)) * v.dtype.itemsize
+        assert 0 <= start and int(start) * v.dtype.itemsize + v.nbytes <= self.nbytes, (start, shape, self.shape)
+        v.ptr = self.ptr + int(start) * v.dtype.itemsize
+        v._base = self
+        return v
+
+    def __getitem__(self, i):
+        """buf[i], i an integer: the contiguous block at index i of the leading axis, as a view."""
+        n = self.shape[0]
+        i = int(i) + (n if int(i) < 0 else 0)
+        if not 0 <= i < n:
+            raise IndexError(f'index {i} out of range for a leading axis of {n}')
+        return self.part(i * int(np.prod(self.shape[1:], dtype=np.int64)), self.shape[1:])
 
     def free(self):
         if getattr(self, 'ptr', None) and not hasattr(self, '_base'):
@@ -60,6 +82,12 @@ class DevBuf:
 def _ptr(buf):
     """Device pointer of an optional output the method allocated, NULL for one not asked for."""
     return buf.ptr if buf is not None else None
+
+
+def _on_host(a):
+    """Neither a DevBuf nor a torch tensor: a NumPy array or whatever np.asarray takes -- a method that follows the container rule
+    (NumPy in, NumPy out; device in, DevBuf out) answers such an input with a NumPy array."""
+    return not (isinstance(a, DevBuf) or hasattr(a, 'data_ptr'))
 
 
 def parse_mask_type(mask):
@@ -215,6 +243,83 @@ class Engine:
         m = self.empty((n_sig, self.T, self.F), np.float32)
         self._chk(self.lib.disco_mask_ivad(self.ctx, ps, n_sig, m.ptr, self.stream))
         return m
+
+    # ---- from reverberated sources to rooms (convolve_signals.py:102-115, 255-273; post_generator.py:99-115).  The conventions of
+    # disco_amd.metrics: the last axis is time, the leading axes a batch; NumPy in gives NumPy out, a device array in gives a DevBuf
+    @staticmethod
+    def _lead_stops(stop, lead, L):
+        """`stop` (None, a scalar, or an array broadcast over the leading axes) -> None or one int per flattened signal, each in [0, L]."""
+        if stop is None:
+            return None
+        try:
+            stops = np.ascontiguousarray(np.broadcast_to(np.asarray(stop), tuple(lead))).reshape(-1)
+        except ValueError:
+            raise ValueError(f'stop of shape {np.shape(stop)} does not broadcast to the leading axes {tuple(lead)}') from None
+        if not np.issubdtype(stops.dtype, np.integer):
+            raise ValueError(f'stop must hold integers, got {stops.dtype}')
+        if np.any(stops < 0) or np.any(stops > L):
+            raise ValueError(f'need 0 <= stop <= L = {L}: stop {stop}')
+        return stops.astype(np.int32)
+
+    def vad_samples(self, x, stop=None, win_len=512, win_hop=256, thr=0.001, rat=2):
+        """x (..., L) float32 -> the per-sample VAD (..., L) of 0.0 / 1.0: vad_oracle_batch (sigproc_utils.py:12-55) of every signal
+        (disco_vad_samples).  stop: signal i is processed as if sliced to stop[i] and run alone; zeros at and beyond it."""
+        host = _on_host(x)
+        if host:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        shape = tuple(int(v) for v in x.shape)
+        lead, L = shape[:-1], shape[-1]
+        n_sig = int(np.prod(lead, dtype=np.int64))
+        stops = self._lead_stops(stop, lead, L)
+        px, kx = self.to_device(x, np.float32)
+        pst, kst = self.to_device(stops, np.int32)
+        vad = self.empty(shape, np.float32)
+        self._chk(self.lib.disco_vad_samples(self.ctx, px, n_sig, L, pst, win_len, win_hop, thr, rat, vad.ptr, self.stream))
+        return vad.numpy() if host else vad
+
+    def mix_scaled(self, s, n, gain, group=1, stop=None, want_n=True, want_y=True, n_out=None, y_out=None):
+        """s (..., L) or None, n (..., Ln) with Ln <= L, gain: one float per `group` consecutive signals (a scalar serves all)
+        -> (n_out, y_out), each (..., L) or None where not wanted: n_out = gain * n below min(Ln, stop), y_out = s + n_out below stop, exact
+        zeros elsewhere (disco_mix_scaled); y_out - s == n_out bit for bit.  s = None: the scaled noise alone (want_y is then ignored).
+        n_out / y_out: optional caller-owned device arrays to write into (n_out may be n itself when Ln == L); they are returned as given."""
+        host = _on_host(n)
+        if host:
+            n = np.ascontiguousarray(n, dtype=np.float32)
+        if s is not None and _on_host(s):
+            s = np.ascontiguousarray(s, dtype=np.float32)
+        nshape = tuple(int(v) for v in n.shape)
+        lead, Ln = nshape[:-1], nshape[-1]
+        L = Ln if s is None else int(s.shape[-1])
+        if s is not None and tuple(int(v) for v in s.shape[:-1]) != lead:
+            raise ValueError(f's and n must share their leading axes: {tuple(s.shape)} and {nshape}')
+        if Ln > L:
+            raise ValueError(f'the noise ({Ln} samples) is longer than the signal ({L})')
+        want_y = (want_y or y_out is not None) and s is not None
+        want_n = want_n or n_out is not None
+        if not (want_n or want_y):
+            raise ValueError('nothing asked for: want_n or want_y (with s given)')
+        n_sig = int(np.prod(lead, dtype=np.int64))
+        if group < 1 or n_sig % group:
+            raise ValueError(f'{n_sig} signals are no multiple of group = {group}')
+        if _on_host(gain):
+            try:
+                gain = np.ascontiguousarray(np.broadcast_to(np.asarray(gain, dtype=np.float32).reshape(-1), (n_sig // group,)))
+            except ValueError:
+                raise ValueError(f'gain of shape {np.shape(gain)} does not give one value per {group} of {n_sig} signals') from None
+        stops = self._lead_stops(stop, lead, L)
+        pn, kn = self.to_device(n, np.float32)
+        ps, ks = self.to_device(s if want_y else None, np.float32)
+        pg, kg = self.to_device(gain, np.float32)
+        pst, kst = self.to_device(stops, np.int32)
+        pno = pyo = None
+        fresh_n, fresh_y = n_out is None, y_out is None                      # a fresh output follows the container of n
+        if want_n:
+            n_out, pno, kno = self._out(n_out, lead + (L,), np.float32, 'size')
+        if want_y:
+            y_out, pyo, kyo = self._out(y_out, lead + (L,), np.float32, 'size')
+        self._chk(self.lib.disco_mix_scaled(self.ctx, ps, pn, n_sig, L, Ln, pg, group, pst, pno, pyo, self.stream))
+        return ((n_out.numpy() if host and fresh_n else n_out) if want_n else None,
+                (y_out.numpy() if host and fresh_y else y_out) if want_y else None)
 
     # ---- the step before the path (SURVEY 8f-4; gen_disco/convolve_signals.py:160-163)
     def rir_convolve(self, dry, rir, out_len=None):

@@ -285,7 +285,7 @@ def _band_levels(x, b, a, start, stop, gate=None):
     x2, lead = _flat(x)
     g2 = None
     if gate is not None:
-        if isinstance(gate, np.ndarray) or not hasattr(gate, 'data_ptr'):
+        if isinstance(gate, np.ndarray) or not (hasattr(gate, 'data_ptr') or hasattr(gate, 'ptr')):       # a host array (not a tensor, not a DevBuf)
             gate = np.broadcast_to(np.asarray(gate, dtype=np.float32), lead + (x2.shape[-1],))       # one VAD for the whole batch is fine
         g2, _ = _flat(gate)
     st = _engine().band_stats(x2, b, a, start, _span_stops(stop, lead), gate=g2).numpy()
@@ -297,7 +297,7 @@ def _band_levels2(x, y, b, a, start, stop):
     is (signal, band) -- stacking both batches doubles the waves in flight."""
     x2, lead = _flat(x)
     y2, lead_y = _flat(y)
-    if lead != lead_y or type(x2) is not type(y2):
+    if lead != lead_y or type(x2) is not type(y2) or hasattr(x2, 'ptr'):          # (two DevBufs cannot be stacked: one launch each)
         return _band_levels(x, b, a, start, stop), _band_levels(y, b, a, start, stop)
     if isinstance(x2, np.ndarray):
         both = np.concatenate([x2, y2], 0)

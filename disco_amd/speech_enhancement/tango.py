@@ -110,10 +110,11 @@ def offline_tango_batched(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_
     MODES = ('local', None, 'distant', 'compressed', 'use_oracle_refs', 'use_oracle_zs', 'previous')
     if mask_for_z not in MODES:
         raise NotImplementedError(f'mask_for_z must be one of {MODES}')       # 'use_oracle_sigs' is broken in the reference
-    y = np.ascontiguousarray(y, dtype=np.float32)
-    s = np.ascontiguousarray(s, dtype=np.float32)
-    n = np.ascontiguousarray(n, dtype=np.float32)
-    R, K, M, L = y.shape
+    on_device = lambda a: hasattr(a, 'data_ptr') or hasattr(a, 'ptr')            # a torch tensor or a DevBuf (dataset_utils.mix_rooms): read in place
+    if any(on_device(a) for a in (y, s, n)) and not (vads[0] == vads[1] and vads[0][:-1] in ('irm', 'ibm', 'iam')):
+        raise NotImplementedError('device-resident y, s, n need one TF mask type for both steps: every other mask is prepared from host copies')
+    y, s, n = (a if on_device(a) else np.ascontiguousarray(a, dtype=np.float32) for a in (y, s, n))
+    R, K, M, L = (int(v) for v in y.shape)
     if mask_for_z == 'compressed' and vads[0] in ('ivad', 'crnn') and steps & 2:
         raise NotImplementedError("mask_for_z='compressed' needs a TF mask type at step 1 (the reference passes neither a time signal nor z to get_mask there, tango.py:403)")
     eng = get_engine(rooms=R, nodes=K, mics=M, length=L, n_fft=n_fft, mask=_engine_mask_type(vads[0]), pad_mode=pad_mode,

@@ -667,6 +667,34 @@ int disco_ism_rir(disco_ctx* ctx, const float* room_dims, const float* absorptio
                   int64_t n_room, int n_src, int n_mic, int max_order, float fs, float c_sound,
                   float* rir, int rir_len, disco_stream s);
 
+/* ---- from reverberated sources to rooms: the per-sample VAD of the images and the scaled mix -----------------------
+ * disco_vad_samples: vad_oracle_batch (sigproc_utils.py:12-55; get_convolved_vads, convolve_signals.py:102-115) for a batch, one
+ * decision per SAMPLE.  x [n_sig][len] -> vad [n_sig][len] of exact 0.f / 1.f.  stop: device array of n_sig int32, clamped into
+ * [0, len], or NULL (= len).  Signal i is processed as if it had been sliced to L_i = stop[i] and run alone: nothing at or beyond L_i
+ * is read (NaN may sit there), vad is exact zeros at and beyond L_i, L_i == 0 gives all zeros and reads nothing.
+ * Arithmetic (that of disco_mask_ivad, whose decision at frame t is vad[t * win_hop]): mean accumulated in float64 and rounded to
+ * float32; x2 = |(x - mean)^2| in float32; threshold thr * the 0.99-quantile of x2 with NumPy's linear interpolation (radix select);
+ * #(x2 > threshold) per hop segment.  Window n covers [n win_hop, min(n win_hop + win_len, L)) for n < N_w = ceil((L - win_len) /
+ * win_hop + 1) (0 when that is <= 0: L <= win_len - win_hop has no window and an all-zero VAD, as the reference); it is active iff its
+ * count >= N_ / rat (integer division, N_ its clipped length); a sample is 1 iff an active window covers it.
+ * DISCO_E_ARG, nothing written: win_len < 1, win_hop < 1, win_len % win_hop != 0, rat < 1, thr negative or not finite, a null x or
+ * vad, n_sig < 0.  DISCO_E_UNSUPPORTED: len > 4096 * win_hop (the hop counters live in LDS).  One workgroup per signal: row i has the
+ * same bits whatever else is in the batch, and a NaN inside signal i changes no bit of any other row. */
+int disco_vad_samples(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len, const int32_t* stop, int win_len, int win_hop,
+                      float thr, int rat, float* vad, disco_stream s);
+
+/* disco_mix_scaled: the noise scaled by a gain and mixed in, in one pass (the last line of increase_to_snr, sigproc_utils.py:212, 223;
+ * PostGenerator.mix_sigs, dataset_utils/post_generator.py:103-113).  s [n_sig][len], n [n_sig][n_len] with n_len <= len (the reference
+ * adds a shorter noise into a zero buffer); gain: device float, one per `group` consecutive signals (one gain per room serves all its
+ * channels; group = 1: one per signal), n_sig % group == 0; stop as above, L_i = stop[i].
+ *   n_out[i][t] = gain[i / group] * n[i][t]  for t < min(n_len, L_i), exact zero elsewhere in [0, len)
+ *   y_out[i][t] = s[i][t] + n_out[i][t]      for t < L_i,             exact zero elsewhere
+ * y_out is the sum with the ROUNDED product stored in n_out (no fused multiply-add): y_out - s == n_out.  n_out or y_out may be NULL,
+ * not both; s may be NULL iff y_out is.  n_out == n (in place) is allowed when n_len == len.  Nothing of s or n at or beyond L_i is
+ * read.  16-byte accesses when len and n_len are multiples of 4 and every array is 16-byte aligned, one float at a time otherwise. */
+int disco_mix_scaled(disco_ctx* ctx, const float* s, const float* n, int64_t n_sig, int64_t len, int64_t n_len, const float* gain,
+                     int group, const int32_t* stop, float* n_out, float* y_out, disco_stream st);
+
 /* ---- self-test of the packed complex arithmetic the FFT / covariance / filter kernels are written on ---------------
  * (disco_amd/csrc/pk.h: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 with op_sel / neg modifiers; no reference counterpart --
  * it pins the instruction encodings against their C++ statement, which is what the CPU-side kernel tests execute.)
