@@ -196,8 +196,10 @@ extern "C" void disco_destroy(disco_ctx* ctx) {
     stage_clear(ctx);
     if (ctx->d_win) (void)hipFree(ctx->d_win);
     if (ctx->d_tw) (void)hipFree(ctx->d_tw);
-    for (DevBlock* b : {&ctx->own_ws, &ctx->partials.full, &ctx->partials.tail, &ctx->conv_ws})
+    for (DevBlock* b : {&ctx->own_ws, &ctx->partials.full, &ctx->partials.tail, &ctx->conv_ws, &ctx->src_ws})
         if (b->p) (void)hipFree(b->p);
+    for (c32* t : ctx->src_tw)
+        if (t) (void)hipFree(t);
     if (ctx->d_tw_conv && ctx->d_tw_conv != ctx->d_tw) (void)hipFree(ctx->d_tw_conv);
     if (ctx->d_lens_own) (void)hipFree(ctx->d_lens_own);
     delete ctx;

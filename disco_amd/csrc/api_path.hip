@@ -343,7 +343,7 @@ extern "C" size_t disco_reference_workspace_bytes(const disco_ctx* ctx) { return
 
 extern "C" size_t disco_owned_bytes(const disco_ctx* ctx) {
     size_t n = 0;
-    if (ctx) for_family(ctx, [&n](const disco_ctx* x) { n += partials_bytes(x) + x->own_ws.bytes + x->conv_ws.bytes; });
+    if (ctx) for_family(ctx, [&n](const disco_ctx* x) { n += partials_bytes(x) + x->own_ws.bytes + x->conv_ws.bytes + x->src_ws.bytes; });
     return n;
 }
 

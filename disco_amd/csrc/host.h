@@ -90,6 +90,8 @@ struct disco_ctx {
     const void *ref_y = nullptr, *ref_s = nullptr, *ref_n = nullptr;   // ... and the inputs that state was computed from
     c32* d_tw_conv = nullptr;        // 1024-point twiddles of disco_rir_convolve (== d_tw when n_fft is 1024), lazy
     DevBlock conv_ws;                // its spectra workspace, lazy
+    c32* src_tw[23] = {};            // twiddle tables of disco_noise_from_signal, one per n_fft = 2^p (api_sources.hip), lazy
+    DevBlock src_ws;                 // its two complex planes, lazy
     int k0 = 0, Kl = 0;              // node shard: this context holds nodes [k0, k0 + Kl) of every room (default 0, K)
     int zblk = 0;                    // layout of the exchanged-signal arguments Zs / Zn / Z (disco_set_z_blocks; default K = plain)
     int tune_runw = 0, tune_cov_chunks = 0, tune_step2_chunks = 0, tune_pairs = 0;   // disco_set_tuning overrides (0 = batch-size heuristic)

@@ -5,8 +5,9 @@ Arrays may be given as numpy arrays (copied host->device through the library's o
 All compute happens in libdisco_hip.so; this file only marshals pointers.  No CPU fallback exists.
 The marshalling is stated once, in the helpers under "plumbing": `_out` (caller-owned or fresh output), `_alias` (a second argument that
 may be the first), `_ptr` (optional buffer -> pointer or NULL), `_span_stops` / `_span_stops_dev` (`stop` of a metric), `_chunk_plan` /
-`_chunks` (a batch walked under a workspace budget), `_pencils` (the solvers' prologue), `_selftest_pair`, `_on_host` / `_lead_stops` (the
-container rule and the `stop` over leading axes of vad_samples / mix_scaled); each method names its dialect.
+`_chunks` (a batch walked under a workspace budget), `_pencils` (the solvers' prologue), `_selftest_pair`, `_on_host` / `_lead_stops` / `_lead_values`
+(the container rule, the `stop` and the other per-signal values over leading axes of vad_samples / mix_scaled / noise_from_signal /
+affine_segment); each method names its dialect.
 """
 import ctypes as C
 
@@ -320,6 +321,84 @@ class Engine:
         self._chk(self.lib.disco_mix_scaled(self.ctx, ps, pn, n_sig, L, Ln, pg, group, pst, pno, pyo, self.stream))
         return ((n_out.numpy() if host and fresh_n else n_out) if want_n else None,
                 (y_out.numpy() if host and fresh_y else y_out) if want_y else None)
+
+    # ---- dry sources (dataset_utils/signal_setups.py:42-138): the same conventions
+    @staticmethod
+    def _lead_values(v, lead, dtype, name):
+        """One value per flattened signal from None (-> None: the C side's default), a scalar or an array broadcast over the leading axes."""
+        if v is None:
+            return None
+        try:
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v), tuple(lead)), dtype=dtype).reshape(-1)
+        except ValueError:
+            raise ValueError(f'{name} of shape {np.shape(v)} does not broadcast to the leading axes {tuple(lead)}') from None
+
+    def noise_from_signal(self, x, phase, stop=None, n_fft=None, max_workspace=1 << 30, out=None):
+        """x (..., L) float32, phase (..., n_fft / 2 + 1) float32 in turns, [0, 1) -> (..., L): irfft(|rfft(x_i[:stop_i], n_fft)| *
+        exp(2 pi i phase_i), n_fft)[:stop_i], zeros at and beyond stop_i (disco_noise_from_signal; sigproc_utils.py:257-279 with the
+        phases given).  n_fft: a power of two from 2^10 to 2^22, by default the smallest that holds the longest signal.  The batch is
+        walked in chunks of signals so that the transform's workspace in the context (8 n_fft bytes per signal) stays under
+        max_workspace bytes; one signal always goes.  out: an optional caller-owned device array of as many elements, returned as given."""
+        from .math_utils import next_pow_2
+        host = _on_host(x)
+        if host:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        shape = tuple(int(v) for v in x.shape)
+        lead, L = shape[:-1], shape[-1]
+        n_sig = int(np.prod(lead, dtype=np.int64))
+        stops = self._lead_stops(stop, lead, L)
+        longest = L if stops is None else int(stops.max(initial=0))
+        n_fft = max(next_pow_2(max(longest, 1)), 1024) if n_fft is None else int(n_fft)
+        if n_fft < 1 or n_fft & (n_fft - 1):
+            raise ValueError(f'n_fft must be a power of two: {n_fft}')
+        if longest > n_fft:
+            raise ValueError(f'a signal of {longest} samples does not fit n_fft = {n_fft}')
+        if _on_host(phase):
+            phase = np.ascontiguousarray(phase, dtype=np.float32)
+        if tuple(int(v) for v in phase.shape) != lead + (n_fft // 2 + 1,):
+            raise ValueError(f'phase must be {lead + (n_fft // 2 + 1,)} for n_fft = {n_fft}: {tuple(phase.shape)}')
+        px, kx = self.to_device(x, np.float32)
+        pp, kp = self.to_device(phase, np.float32)
+        pst, kst = self.to_device(stops, np.int32)
+        fresh = out is None
+        out, po, ko = self._out(out, shape, np.float32, 'size')
+        step = max(1, int(max_workspace) // (8 * n_fft))
+        for i0 in range(0, n_sig, step):
+            m = min(step, n_sig - i0)
+            self._chk(self.lib.disco_noise_from_signal(self.ctx, px + 4 * i0 * L, m, L, None if pst is None else pst + 4 * i0, n_fft,
+                                                       pp + 4 * i0 * (n_fft // 2 + 1), po + 4 * i0 * L, self.stream))
+        return out.numpy() if host and fresh else out
+
+    def affine_segment(self, x, stop=None, start=None, count=None, mean=None, gain=None, lead=0, out_len=None, out=None):
+        """x (..., L) float32 -> (..., out_len), out_len = lead + L by default:
+            out[i, lead + t] = float32((float64(x[i, (start_i + t) % L_i]) - mean_i) * gain_i)    for 0 <= t < min(count_i, out_len - lead)
+        and exact zeros elsewhere (disco_affine_segment), L_i = stop_i.  stop, start, count (integers), mean, gain (float64): None (L,
+        0, L_i, 0, 1), a scalar, or an array broadcast over the leading axes.  out: an optional caller-owned device array of as many
+        elements, returned as given."""
+        host = _on_host(x)
+        if host:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        shape = tuple(int(v) for v in x.shape)
+        lead_axes, L = shape[:-1], shape[-1]
+        n_sig = int(np.prod(lead_axes, dtype=np.int64))
+        lead = int(lead)
+        out_len = lead + L if out_len is None else int(out_len)
+        if not 0 <= lead <= out_len:
+            raise ValueError(f'need 0 <= lead <= out_len: lead {lead}, out_len {out_len}')
+        stops = self._lead_stops(stop, lead_axes, L)
+        for name, v in (('start', start), ('count', count)):
+            if v is not None and not np.issubdtype(np.asarray(v).dtype, np.integer):
+                raise ValueError(f'{name} must hold integers, got {np.asarray(v).dtype}')
+        px, kx = self.to_device(x, np.float32)
+        pst, kst = self.to_device(stops, np.int32)
+        psa, ksa = self.to_device(self._lead_values(start, lead_axes, np.int32, 'start'), np.int32)
+        pc, kc = self.to_device(self._lead_values(count, lead_axes, np.int32, 'count'), np.int32)
+        pm, km = self.to_device(self._lead_values(mean, lead_axes, np.float64, 'mean'), np.float64)
+        pg, kg = self.to_device(self._lead_values(gain, lead_axes, np.float64, 'gain'), np.float64)
+        fresh = out is None
+        out, po, ko = self._out(out, lead_axes + (out_len,), np.float32, 'size')
+        self._chk(self.lib.disco_affine_segment(self.ctx, px, n_sig, L, pst, psa, pc, pm, pg, lead, po, out_len, self.stream))
+        return out.numpy() if host and fresh else out
 
     # ---- the step before the path (SURVEY 8f-4; gen_disco/convolve_signals.py:160-163)
     def rir_convolve(self, dry, rir, out_len=None):

@@ -6,6 +6,15 @@ from ._engines import get_engine
 N_FFT, N_HOP = 512, 256
 
 
+def next_pow_2(x):
+    """The smallest power of two that is not below x, in integers: the reference's int(pow(2, np.ceil(np.log2(x))))
+    (math_utils.py:155-165) for every 1 <= x <= 2^22 + 1, without its float64 logarithm."""
+    x = int(x)
+    if x < 1:
+        raise ValueError(f'next_pow_2 needs x >= 1: {x}')
+    return 1 << (x - 1).bit_length()
+
+
 def my_stft(x):
     """librosa STFT with the reference's parameters (n_fft=512, hop=256, center=True).  x: (L,) -> (257, T) complex64."""
     x = np.ascontiguousarray(x, dtype=np.float32)

@@ -695,6 +695,39 @@ int disco_vad_samples(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len
 int disco_mix_scaled(disco_ctx* ctx, const float* s, const float* n, int64_t n_sig, int64_t len, int64_t n_len, const float* gain,
                      int group, const int32_t* stop, float* n_out, float* y_out, disco_stream st);
 
+/* ---- dry sources: speech-shaped noise and the levelling pass (dataset_utils/signal_setups.py:42-138) ---------------
+ * disco_noise_from_signal: noise_from_signal (sigproc_utils.py:257-279) for a batch -- noise with the magnitude spectrum of the signal
+ * and the phases the caller drew.  x [n_sig][len]; stop: device array of n_sig int32 or NULL (= len), L_i = stop[i] clamped into
+ * [0, min(len, n_fft)]; phase [n_sig][n_fft / 2 + 1] float32 in TURNS, in [0, 1) -- the reference's np.random.random(X.shape[-1]);
+ * out [n_sig][len].  Per signal, with NumPy's conventions:
+ *   X = rfft(x_i[:L_i], n_fft) (zero-padded);  Y_k = |X_k| (cos 2 pi u_k + i sin 2 pi u_k);  out_i[:L_i] = irfft(Y, n_fft)[:L_i]
+ * (the imaginary parts of Y_0 and Y_{n_fft/2} do not enter, the scale is 1 / n_fft); out_i is exact zeros in [L_i, len).  Nothing of
+ * x_i at or beyond L_i is read (NaN may sit there); L_i == 0 writes zeros and reads nothing.  u is reduced in turns before the sine
+ * and cosine are taken (sincospif(2 u)), so the error of the factor does not grow with the angle.
+ * n_fft = 2^p, 10 <= p <= 22 (513 samples to 262 s at 16 kHz); any other power of two: DISCO_E_UNSUPPORTED.  DISCO_E_ARG, nothing
+ * written: n_fft no power of two, n_fft < len while stop is NULL, a null x, phase or out, n_sig < 0.
+ * The transform is a multi-pass Stockham schedule over the half-length complex signal x[2 n] + i x[2 n + 1], its radices the 512- and
+ * 1024-point wave transforms and register DFTs of 4, 8, 16 (disco_amd/csrc/k_sources.h); its twiddles come from a float64 table the
+ * context caches per n_fft, its two complex planes (8 n_fft bytes per signal) are the context's own and lazy: the first call for a
+ * new n_fft or a larger batch allocates and uploads, every later call is a fixed sequence of launches.  No atomics: row i has the
+ * same bits whatever else is in the batch, and a NaN in row i changes no bit of another row. */
+int disco_noise_from_signal(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len, const int32_t* stop, int64_t n_fft,
+                            const float* phase, float* out, disco_stream s);
+
+/* disco_affine_segment: subtract, scale, shift, wrap in one launch -- the levelling of get_target_segment (signal_setups.py:54-69:
+ * start = 0, lead = fs) and the rolled, de-meaned cut of _read_random_signal (:133-136: np.roll(sig, len - rnd_start)[:n] is
+ * sig[(rnd_start + t) mod len], lead = 0).  x [n_sig][len] -> out [n_sig][out_len]; L_i = stop[i] clamped into [0, len];
+ *   out[i][lead + t] = (float)(((double)x[i][(start_i + t) mod L_i] - mean_i) * gain_i)    for 0 <= t < min(count_i, out_len - lead)
+ * and exact zeros everywhere else in [0, out_len).  stop, start, count: device int32 per signal, mean, gain: device float64 per
+ * signal; NULL stands for L_i = len, start = 0, count = L_i, mean = 0, gain = 1.  start is taken mod L_i, a negative count as 0;
+ * count_i > L_i repeats the signal periodically; L_i == 0 gives zeros and reads nothing.  The subtraction and the product are each
+ * rounded in float64, then once to float32.  DISCO_E_ARG, nothing written: lead < 0 or lead > out_len, a null x or out, n_sig < 0.
+ * 16-byte accesses when len and out_len are multiples of 4 and both arrays are 16-byte aligned (a quad of sources that is not one
+ * aligned run is still read by element), one float at a time otherwise. */
+int disco_affine_segment(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len, const int32_t* stop, const int32_t* start,
+                         const int32_t* count, const double* mean, const double* gain, int lead, float* out, int64_t out_len,
+                         disco_stream s);
+
 /* ---- self-test of the packed complex arithmetic the FFT / covariance / filter kernels are written on ---------------
  * (disco_amd/csrc/pk.h: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 with op_sel / neg modifiers; no reference counterpart --
  * it pins the instruction encodings against their C++ statement, which is what the CPU-side kernel tests execute.)
