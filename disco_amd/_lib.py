@@ -83,6 +83,8 @@ PROTOTYPES = {
     'disco_ism_rir': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _f, _f, _vp, _int, _vp]),
     'disco_vad_samples': (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _f, _int, _vp, _vp]),
     'disco_mix_scaled': (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp]),
+    'disco_source_mix': (_int, [_vp, _vp, _int, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    'disco_source_masks': (_int, [_vp, _vp, _int, _i64, _vp, _vp, _vp]),
     'disco_noise_from_signal': (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     'disco_affine_segment': (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp]),
     'disco_gru_gates':(_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp]),

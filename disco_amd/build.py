@@ -24,8 +24,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fno-slp-vectorize', '-f
 # (the rank-R solves, csrc/k_gevd_full.h): none -- their matrices live in registers with compile-time indices only.  k_gevd_mwf_r1_wide and
 # k_cov_wide (17 <= P <= 32, csrc/k_solve_wide.h, csrc/k_cov_wide.h): none -- the wide solver's matrices live in LDS, the covariance's
 # accumulators in registers.  k_estoi_corr, k_estoi_finish (csrc/k_estoi.h): none -- a column's 2 x 15 float64 values stay in registers.
+# k_source_masks (csrc/k_stft.h): none -- the spectra of all talkers of a frame live in registers (the 1024-point plans of 5 to 8 talkers
+# lean on the accumulator half of the file: 76 and 144 copies).  k_source_mix: none -- the channel targets are read from the arguments.
 SCRATCH_LIMIT = {'k_room_cov_dma': 64, 'k_gevd_mwf_r1_dpp': 0, 'k_apply_istft_wide': 0, 'k_gevd_full': 0, 'k_gevd_mwf_r1_wide': 0,
-                 'k_cov_wide': 0, 'k_estoi_corr': 0, 'k_estoi_finish': 0}
+                 'k_cov_wide': 0, 'k_estoi_corr': 0, 'k_estoi_finish': 0, 'k_source_masks': 0, 'k_source_mix': 0}
 # units whose kernels read other lanes' registers through DPP inside inline asm (csrc/dpp64.h): hipcc cannot see those reads, so
 # the two DPP hazards (a VALU write of the source within 2 wait states, an EXEC write within 5) are checked on the device
 # assembly of the unit (disco_amd/check_dpp_hazards.py) and a build with a hazard is refused

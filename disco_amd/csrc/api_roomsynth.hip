@@ -48,3 +48,30 @@ extern "C" int disco_mix_scaled(disco_ctx* ctx, const float* s, const float* n, 
                            y_out, (long long)n_sig, (int)len, (int)n_len);
     return check_launch(ctx, "k_mix_scaled");
 }
+
+// ---- a meeting room of S talkers: mix, own talker and the sum of the others per channel (simulate_room, gen_meetit/convolve_signals.py:140-148)
+
+extern "C" int disco_source_mix(disco_ctx* ctx, const float* images, int n_src, int64_t n_row, int64_t len, const int32_t* target, int n_mic,
+                                const int32_t* stop, float* y_out, float* s_out, float* n_out, disco_stream st) {
+    DISCO_ENTER(ctx);
+    if (!images || !target || (!y_out && !s_out && !n_out) || n_row < 0 || len < 0) return fail(ctx, DISCO_E_ARG, "disco_source_mix: bad argument");
+    if (n_src < 2 || n_src > MIX_MAX_SOURCES) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_source_mix: the number of sources must be 2 <= n_src <= 8");
+    if (n_mic < 1 || n_row % n_mic != 0) return fail(ctx, DISCO_E_ARG, "disco_source_mix: n_row must be a multiple of n_mic >= 1");
+    if (n_mic > MIX_MAX_CHANNELS) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_source_mix: more than 64 channels per room");
+    MixTargets tg = {};
+    for (int c = 0; c < n_mic; ++c) {
+        if (target[c] < 0 || target[c] >= n_src) return fail(ctx, DISCO_E_ARG, "disco_source_mix: target must name a source, 0 <= target[c] < n_src");
+        tg.t[c] = (unsigned char)target[c];
+    }
+    if (len > 0x7fffffffLL - MIX_CHUNK) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_source_mix: signals longer than 2^31 - 1025 samples");
+    if (n_row == 0 || len == 0) return 0;
+    const long long items = (long long)n_row * ((len + MIX_CHUNK - 1) / MIX_CHUNK);
+    const dim3 grid((unsigned)std::min<long long>(items, 1 << 16));
+    const uintptr_t bits = (uintptr_t)images | (uintptr_t)y_out | (uintptr_t)s_out | (uintptr_t)n_out;      // NULL adds nothing
+    with_bool(len % 4 == 0 && (bits & 15) == 0, [&](auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_source_mix<VEC>), grid, dim3(MIX_THREADS), 0, (hipStream_t)st, images, n_src, tg, n_mic, (const int*)stop,
+                           y_out, s_out, n_out, (long long)n_row, (int)len);
+    });
+    return check_launch(ctx, "k_source_mix");
+}

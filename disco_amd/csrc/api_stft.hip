@@ -92,6 +92,37 @@ extern "C" int disco_mask_oracle(disco_ctx* ctx, const float* s_ref, const float
     return check_launch(ctx, "k_mask_oracle");
 }
 
+// ---- a meeting room: every talker's mask against the sum of the others, and the mix spectrum (get_masks, gen_meetit/convolve_signals.py:166-188)
+
+extern "C" int disco_source_masks(disco_ctx* ctx, const float* images, int n_src, int64_t n_sig, float* masks, disco_c32* mix, disco_stream s) {
+    DISCO_ENTER(ctx);
+    if (!images || !masks || n_sig < 1) return fail(ctx, DISCO_E_ARG, "disco_source_masks: bad argument");
+    if (n_src < 2 || n_src > 8) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_source_masks: the number of sources must be 2 <= n_src <= 8");
+    const disco_cfg& c = ctx->cfg;
+    if (c.mask_type < DISCO_MASK_IRM || c.mask_type > DISCO_MASK_IAM)
+        return fail(ctx, DISCO_E_ARG, "disco_source_masks: unknown mask type");
+    int spr = 1;
+    const int rcl = lengths_sig_per_room(ctx, n_sig, "disco_source_masks", &spr);
+    if (rcl) return rcl;
+    const int runs = stft_runs(ctx->T);
+    const long long n_items = (long long)n_sig * runs;
+    if (stft_blocks(n_items) > 0x7fffffffLL)
+        return fail(ctx, DISCO_E_UNSUPPORTED, "disco_source_masks: batch too large for one launch");
+    const float thr = powf(10.f, c.mask_bin_thr_db / 10.f);                 // math_utils.py db2lin (power)
+    const dim3 grid((unsigned)stft_blocks(n_items));
+    StageScope stage_scope_(ctx, s, "source_masks");
+    with_bool(c.n_fft == 512, [&](auto n512) {
+        for_int<1, 4>((n_src + 1) / 2, [&](auto np) {
+            constexpr int N = decltype(n512)::value ? 512 : 1024, NP = decltype(np)::value;
+            constexpr bool PREFETCH = source_masks_prefetch(N, NP);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_source_masks<N, NP, PREFETCH>), grid, dim3(64 * STFT_WAVES), 0, (hipStream_t)s, images, masks,
+                               (c32*)mix, ctx->d_win, ctx->d_tw, n_src, (long long)n_sig, c.length, ctx->T, c.pad_mode, c.mask_type, c.mask_pow,
+                               thr, runs, n_items, ctx->d_lens, spr);
+        });
+    });
+    return check_launch(ctx, "k_source_masks");
+}
+
 extern "C" int disco_tf_mask(disco_ctx* ctx, const disco_c32* S, const disco_c32* N, int64_t n_elem, int mask_type,
                              int mask_pow, float bin_thr_db, float* mask, disco_stream s) {
     DISCO_ENTER(ctx);

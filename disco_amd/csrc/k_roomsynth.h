@@ -2,6 +2,8 @@
 //   k_vad_samples   vad_oracle_batch (sigproc_utils.py:12-55) with one decision per SAMPLE and a length per signal -- the phases of
 //                   k_vad_mask (k_vad.h: mean, radix-select quantile, counts per hop segment), then window -> segment -> sample
 //   k_mix_scaled    n_out = gain * n (a shorter noise lands in a zero buffer), y_out = s + n_out, zeros beyond a signal's length
+// and a meeting room of S talkers (gen_meetit/convolve_signals.py:140-148, 176-185):
+//   k_source_mix    per channel: the mix of all S images, the image of the channel's own talker, the sum of the others -- one pass
 #pragma once
 #include <cstdint>
 
@@ -128,6 +130,69 @@ static __global__ __launch_bounds__(MIX_THREADS) void k_mix_scaled(const float* 
             for (int j = 0; j < cnt; ++j) {
                 if (n_out) n_out[row * len + t0 + j] = no[j];
                 if (y_out) y_out[row * len + t0 + j] = yo[j];
+            }
+        }
+    }
+}
+
+constexpr int MIX_MAX_SOURCES = 8;
+constexpr int MIX_MAX_CHANNELS = 64;
+// the talker each channel of a room listens to, by value in the kernel's arguments (the host has checked every entry against S)
+struct MixTargets {
+    unsigned char t[MIX_MAX_CHANNELS];
+};
+
+// img [S][n_row][len], row = (room, channel), channel = row % n_mic -> y = ((img_0 + img_1) + img_2) + ..., s = img_tgt, n = the sum over
+// j != tgt in ascending j, tgt = targets.t[channel]; each output [n_row][len] or NULL.  Plain float32 additions in exactly that order (there is
+// no product to fuse, and no sum starts from a zero: -0 stays -0), so every output equals the NumPy float32 sums.  Exact zeros at and beyond
+// L = stop[row], where no input is read.  The work split and VEC are k_mix_scaled's: one float4 per source and thread where len is a
+// multiple of 4 and every array is 16-byte aligned, a float4 that straddles L read by element.
+template <bool VEC>
+static __global__ __launch_bounds__(MIX_THREADS) void k_source_mix(const float* __restrict__ img, int S, MixTargets targets, int n_mic,
+                                                            const int* __restrict__ stop, float* __restrict__ y_out,
+                                                            float* __restrict__ s_out, float* __restrict__ n_out, long long n_row, int len) {
+    const int chunks = (len + MIX_CHUNK - 1) / MIX_CHUNK;
+    const long long items = n_row * chunks;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const long long row = it / chunks;
+        const int t0 = (int)(it - row * chunks) * MIX_CHUNK + (int)threadIdx.x * 4;
+        if (t0 >= len) continue;
+        const int L = stop ? min(max(stop[row], 0), len) : len;
+        const int tgt = targets.t[row % n_mic];
+        const int cnt = VEC ? 4 : min(4, len - t0);
+        float yo[4] = {0.f, 0.f, 0.f, 0.f}, so[4] = {0.f, 0.f, 0.f, 0.f}, no[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t0 < L) {
+            bool first_n = true;
+            for (int j = 0; j < S; ++j) {
+                const float* xr = img + ((long long)j * n_row + row) * len;
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (VEC && t0 + 4 <= L) {
+                    const float4 q = *reinterpret_cast<const float4*>(xr + t0);
+                    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+                } else {
+                    for (int e = 0; e < cnt; ++e)
+                        if (t0 + e < L) v[e] = xr[t0 + e];
+                }
+                const bool own = j == tgt, start_n = !own && first_n;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    yo[e] = j == 0 ? v[e] : yo[e] + v[e];
+                    so[e] = own ? v[e] : so[e];
+                    no[e] = own ? no[e] : (start_n ? v[e] : no[e] + v[e]);
+                }
+                first_n = first_n && own;
+            }                                                                // (a quad that straddles L: the unread samples are +0, and so are their sums)
+        }
+        float* const outs[3] = {y_out, s_out, n_out};
+        const float* const vals[3] = {yo, so, no};
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            if (!outs[o]) continue;
+            float* dst = outs[o] + row * len + t0;
+            if (VEC) {
+                *reinterpret_cast<float4*>(dst) = make_float4(vals[o][0], vals[o][1], vals[o][2], vals[o][3]);
+            } else {
+                for (int e = 0; e < cnt; ++e) dst[e] = vals[o][e];
             }
         }
     }

@@ -370,6 +370,119 @@ __global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_mask_ora
     }
 }
 
+// A meeting room of S talkers (get_masks, gen_meetit/convolve_signals.py:166-188): img [S][n_sig][L] -> masks [S][n_sig][T][F], mask i the
+// tf_mask of talker i's image against the sum of the others, and optionally mix [n_sig][T][F], the spectrum of the sum of all images.
+// With X_j the spectrum of image j: mix = ((X_0 + X_1) + X_2) + ..., N_i = the sum over j != i in ascending j (the transform is linear: the
+// reference transforms the time-domain sums, the difference is rounding).  Streams like k_mask_oracle, with k_stft's register plan:
+// talkers 2p and 2p + 1 share complex FFT p, NP = ceil(S / 2) transforms per frame (the last talker of an odd S rides alone, its partner
+// slot is never read), and all S spectra of the frame stay in registers until its masks are stored -- no spectrum reaches memory but mix.
+// PREFETCH: the next frame's new half-windows are requested before the transforms, as in k_mask_oracle; without it (the widest plans,
+// where those registers are not to be had) after them.  The rules of per-room lengths are k_mask_oracle's.
+constexpr bool source_masks_prefetch(int n, int np) { return n * np <= 2048; }
+template <int N, int NP, bool PREFETCH>
+__global__ DISCO_KERNEL_ALIGN __launch_bounds__(64 * STFT_WAVES) void k_source_masks(const float* __restrict__ img, float* __restrict__ masks,
+                                                                   c32* __restrict__ mix, const float* __restrict__ win,
+                                                                   const c32* __restrict__ tw, int S, long long n_sig, int L, int T,
+                                                                   int pad_mode, int mask_type, int mask_pow, float thr_lin,
+                                                                   int runs_per_sig, long long n_witems, const int* __restrict__ lens,
+                                                                   int sig_per_room) {
+    constexpr int E = FftPlan<N>::E, F = N / 2 + 1, EH = E / 2;
+    __shared__ StftShared<N> sh;
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    const long long item = (long long)blockIdx.x * STFT_WAVES + wave;
+    if (item >= n_witems) return;
+    const long long g = item / runs_per_sig;
+    const int t0 = (int)(item % runs_per_sig) * STFT_RUN;
+    const int Lr = room_length(lens, lens ? g / sig_per_room : 0, L), Tr = lens ? 1 + Lr / (N / 2) : T;      // see k_stft
+    if (lens) {                                    // frames the room does not have: masks and mix FORCED to zero, no sample touched
+        for (int t = max(t0, Tr); t < min(T, t0 + STFT_RUN); ++t) {
+            for (int i = 0; i < S; ++i) {
+                float* mo = masks + ((i * n_sig + g) * T + t) * (long long)F;
+                for (int f = lane; f < F; f += 64) mo[f] = 0.f;
+            }
+            if (mix) {
+                c32* xo = mix + (g * T + t) * (long long)F;
+                for (int f = lane; f < F; f += 64) xo[f] = make_float2(0.f, 0.f);
+            }
+        }
+        if (t0 >= Tr) return;
+    }
+    const int t1 = min(Tr, t0 + STFT_RUN);
+    WaveTw<N> wtw;
+    wtw.init(tw, lane);
+    float w[E];
+    load_window_half<N>(w, win, lane);
+    const float* xa[NP];
+    const float* xb[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        xa[p] = img + ((2 * p) * n_sig + g) * (long long)L;
+        xb[p] = (2 * p + 1 < S) ? img + ((2 * p + 1) * n_sig + g) * (long long)L : xa[p];
+    }
+    c32 raw[NP][E];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) load_frame_slots<N, 0, E>(raw[p], xa[p], xb[p], t0, Lr, pad_mode, lane);
+    for (int t = t0; t < t1; ++t) {
+        const int tn = min(t + 1, Tr - 1);                 // clamped: harmless reload at the end of a run
+        c32 nxt[NP][EH];
+        if constexpr (PREFETCH) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, Lr, pad_mode, lane);
+        }
+        c32 X[2 * NP][EH + 1];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            c32 v[E];
+            apply_window<N>(v, raw[p], w, 2 * p + 1 < S);
+            fft_wave<N>(v, wtw, sh.buf[wave], lane);
+            rfft_pair_untangle<N>(v, sh.buf[wave], lane, [&](int j, int, c32 a, c32 b) {
+                X[2 * p][j] = a;
+                X[2 * p + 1][j] = b;
+            });
+        }
+        if constexpr (!PREFETCH) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) load_frame_slots<N, EH, E>(nxt[p], xa[p], xb[p], tn, Lr, pad_mode, lane);
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int e = 0; e < EH; ++e) {                 // consume the new half-windows before the stores (see k_stft)
+                DISCO_CONSUME(nxt[p][e].x);
+                DISCO_CONSUME(nxt[p][e].y);
+                raw[p][e] = raw[p][e + EH];
+                raw[p][e + EH] = nxt[p][e];
+            }
+        // the masks of the frame, talker by talker; slot EH (the Nyquist bin) is valid in lane 0 alone
+#pragma unroll
+        for (int i = 0; i < 2 * NP; ++i) {
+            if (i < S) {                                   // wave-uniform
+                float* mo = masks + ((i * n_sig + g) * T + t) * (long long)F;
+#pragma unroll
+                for (int j = 0; j <= EH; ++j) {
+                    c32 others = X[i == 0 ? 1 : 0][j];
+#pragma unroll
+                    for (int q = (i == 0 ? 2 : 1); q < 2 * NP; ++q)
+                        if (q != i && q < S) others = cadd(others, X[q][j]);
+                    const float m = tf_mask_value(X[i][j], others, mask_type, mask_pow, thr_lin);
+                    if (j < EH || lane == 0) store_stream4(&mo[lane + 64 * j], m);
+                }
+            }
+        }
+        if (mix) {
+            c32* xo = mix + (g * T + t) * (long long)F;
+#pragma unroll
+            for (int j = 0; j <= EH; ++j) {
+                c32 sum = X[0][j];
+#pragma unroll
+                for (int i = 1; i < 2 * NP; ++i)
+                    if (i < S) sum = cadd(sum, X[i][j]);
+                if (j < EH || lane == 0) xo[lane + 64 * j] = sum;
+            }
+        }
+    }
+}
+
 // element i of a [n_sig][T][F] array lies in a frame its room does not have (per-room lengths; hop = F - 1)
 __device__ __forceinline__ bool tf_beyond_room(const int* __restrict__ lens, long long i, int T, int F, int sig_per_room) {
     const long long gt = i / F;

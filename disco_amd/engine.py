@@ -322,6 +322,34 @@ class Engine:
         return ((n_out.numpy() if host and fresh_n else n_out) if want_n else None,
                 (y_out.numpy() if host and fresh_y else y_out) if want_y else None)
 
+    def source_mix(self, images, target, stop=None, want_y=True, want_s=True, want_n=True):
+        """images (S, ..., n_mic, L), source-major; target: n_mic ints, target[c] in [0, S) the talker channel c listens to
+        -> (y, s, n), each (..., n_mic, L) or None where not wanted: y = ((img_0 + img_1) + img_2) + ..., s = img_target, n = the sum of
+        the others in ascending order -- float32 additions in exactly that order, one pass over the images (disco_source_mix).  stop:
+        None, a scalar, or an array broadcast over (..., n_mic): exact zeros at and beyond it, where nothing is read.  2 <= S <= 8."""
+        host = _on_host(images)
+        if host:
+            images = np.ascontiguousarray(images, dtype=np.float32)
+        shape = tuple(int(v) for v in images.shape)
+        if len(shape) < 3:
+            raise ValueError(f'images must be (S, ..., n_mic, L): {shape}')
+        S, lead, L = shape[0], shape[1:-1], shape[-1]
+        n_mic = lead[-1]
+        tgt = np.asarray(target).reshape(-1)
+        if tgt.shape != (n_mic,) or not np.issubdtype(tgt.dtype, np.integer):
+            raise ValueError(f'target must hold one integer per channel ({n_mic}): {np.shape(target)}, {tgt.dtype}')
+        if not (want_y or want_s or want_n):
+            raise ValueError('nothing asked for: want_y, want_s or want_n')
+        tgt = np.ascontiguousarray(tgt, dtype=np.int32)
+        n_row = int(np.prod(lead, dtype=np.int64))
+        stops = self._lead_stops(stop, lead, L)
+        pi, ki = self.to_device(images, np.float32)
+        pst, kst = self.to_device(stops, np.int32)
+        outs = [self.empty(lead + (L,), np.float32) if w else None for w in (want_y, want_s, want_n)]
+        self._chk(self.lib.disco_source_mix(self.ctx, pi, S, n_row, L, tgt.ctypes.data, n_mic, pst, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                            self.stream))
+        return tuple(o.numpy() if host and o is not None else o for o in outs)
+
     # ---- dry sources (dataset_utils/signal_setups.py:42-138): the same conventions
     @staticmethod
     def _lead_values(v, lead, dtype, name):
@@ -901,6 +929,18 @@ class Engine:
         m = self.empty((n_sig, self.T, self.F), np.float32)
         self._chk(self.lib.disco_mask_oracle(self.ctx, ps, pn, n_sig, m.ptr, self.stream))
         return m
+
+    def source_masks(self, images, want_mix=True):
+        """images (S, n_sig, L), source-major -> (masks (S, n_sig, T, F), mix (n_sig, T, F) complex64 or None): the mask of every
+        talker's image against the sum of the others and the spectrum of the sum of all, in one transform pass (disco_source_masks;
+        get_masks, gen_meetit/convolve_signals.py:166-188).  The mask kind is the engine's.  2 <= S <= 8."""
+        S, n_sig, Ls = (int(v) for v in images.shape)
+        assert Ls == self.Lsamp
+        pi, ki = self.to_device(images, np.float32)
+        m = self.empty((S, n_sig, self.T, self.F), np.float32)
+        mix = self.empty((n_sig, self.T, self.F), np.complex64) if want_mix else None
+        self._chk(self.lib.disco_source_masks(self.ctx, pi, S, n_sig, m.ptr, _ptr(mix), self.stream))
+        return m, mix
 
     def cov_masked(self, X, mask, Zs=None, Zn=None, mask_remote=True, Rss_out=True):
         """X (R,K,T,F,M), mask (R,K,T,F)[, Zs, Zn (R,K,T,F)] -> Rss, Rnn (R,K,F,P,P)   [tango.py:357-364, 433-440]"""

@@ -231,6 +231,20 @@ int disco_tf_mask(disco_ctx* ctx, const disco_c32* S, const disco_c32* N, int64_
 int disco_mask_oracle(disco_ctx* ctx, const float* s_ref, const float* n_ref, int64_t n_sig,
                       float* mask, disco_stream s);
 
+/* The masks of a meeting room of n_src simultaneous talkers and the spectrum of their mix, in one transform pass (get_masks,
+ * dataset_generation/gen_meetit/convolve_signals.py:166-188).  images: float [n_src][n_sig][L], source-major (n_sig = rooms * channels)
+ * -> masks float [n_src][n_sig][T][F] and, unless NULL, mix disco_c32 [n_sig][T][F].  With X_j the STFT of images[j]:
+ *   mix     = ((X_0 + X_1) + X_2) + ...            complex64 sums in ascending j
+ *   N_i     = the sum of X_j over j != i           in ascending j
+ *   masks_i = tf_mask(X_i, N_i)                    cfg.mask_type / mask_pow / mask_bin_thr_db, the arithmetic of disco_tf_mask
+ * The reference transforms the time-domain sums instead; the transform is linear, so the two differ by rounding only.  Two sources
+ * share one complex FFT (ceil(n_src / 2) transforms per frame, against 1 + 2 n_src of separate calls) and no spectrum but mix reaches
+ * memory.  Per-room lengths (disco_set_lengths) as for disco_mask_oracle: signal g of n_sig belongs to room g / (n_sig / cfg.rooms), the
+ * padding reflects at the room's own end, masks and mix are exact zeros in the frames a room does not have, no sample at or beyond a
+ * room's length is read.  A signal's output bits do not depend on the rest of the batch.
+ * DISCO_E_UNSUPPORTED, nothing written: n_src outside 2 <= n_src <= 8.  DISCO_E_ARG: a null images or masks, n_sig < 1. */
+int disco_source_masks(disco_ctx* ctx, const float* images, int n_src, int64_t n_sig, float* masks, disco_c32* mix, disco_stream s);
+
 /* Masked batch spatial covariance -- the loop nests tango.py:357-364 (step 1, P = M, Zs = Zn = NULL)
  * and tango.py:433-440 (step 2, P = M + K - 1).
  *   v_s(t,f) = [ m*X_k ; g_s*Zs_j (j<k) ; g_s*Zs_j (j>k) ],   Rss[f] = mean_t v_s v_s^H
@@ -694,6 +708,22 @@ int disco_vad_samples(disco_ctx* ctx, const float* x, int64_t n_sig, int64_t len
  * read.  16-byte accesses when len and n_len are multiples of 4 and every array is 16-byte aligned, one float at a time otherwise. */
 int disco_mix_scaled(disco_ctx* ctx, const float* s, const float* n, int64_t n_sig, int64_t len, int64_t n_len, const float* gain,
                      int group, const int32_t* stop, float* n_out, float* y_out, disco_stream st);
+
+/* disco_source_mix: a meeting room of n_src talkers per channel, in one pass over the images (simulate_room,
+ * dataset_generation/gen_meetit/convolve_signals.py:140-148: node k listens to talker k, all others are its noise).
+ * images [n_src][n_row][len], source-major, row = room * n_mic + channel; target: HOST array of n_mic int32, target[c] in [0, n_src)
+ * the talker of channel c (read during the call; at most 64 channels); stop: device array of n_row int32 or NULL, as for
+ * disco_mix_scaled.  Each output [n_row][len], any may be NULL but not all:
+ *   y_out[i] = ((images[0][i] + images[1][i]) + images[2][i]) + ...
+ *   s_out[i] = images[target[i % n_mic]][i]
+ *   n_out[i] = the sum of images[j][i] over j != target[i % n_mic], in ascending j
+ * below L_i = stop[i], exact zeros at and beyond it, where nothing of images is read.  Plain float32 additions in exactly that order
+ * (the results equal NumPy's float32 sums bit for bit).  16-byte accesses when len is a multiple of 4 and every array is 16-byte
+ * aligned, one float at a time otherwise.
+ * DISCO_E_UNSUPPORTED, nothing written: n_src outside 2 <= n_src <= 8, n_mic > 64.  DISCO_E_ARG: a target outside [0, n_src), n_row no
+ * multiple of n_mic, a null images or target, no output. */
+int disco_source_mix(disco_ctx* ctx, const float* images, int n_src, int64_t n_row, int64_t len, const int32_t* target, int n_mic,
+                     const int32_t* stop, float* y_out, float* s_out, float* n_out, disco_stream st);
 
 /* ---- dry sources: speech-shaped noise and the levelling pass (dataset_utils/signal_setups.py:42-138) ---------------
  * disco_noise_from_signal: noise_from_signal (sigproc_utils.py:257-279) for a batch -- noise with the magnitude spectrum of the signal
