@@ -16,7 +16,9 @@ PAD_MODES = {'reflect': 0, 'constant': 1}
 FLAG_STAGED_STEP2 = 1
 FLAG_LAZY_SCRATCH = 2
 FLAG_NO_CHILDREN = 4
-ESTOI_SEGS = 64                         # DISCO_ESTOI_SEGS of include/disco_hip.h: segments one workgroup of k_estoi_corr owns
+SEG_SNR_MAX_WIN = 2048                  # DISCO_SEG_SNR_MAX_WIN: the longest window disco_seg_snr takes
+REVERB_MAX_RIR = 8192                   # DISCO_REVERB_MAX_RIR: the longest response disco_rir_split / disco_reverb_energies take
+ESTOI_SEGS = 64                 # DISCO_ESTOI_SEGS of include/disco_hip.h: segments one workgroup of k_estoi_corr owns
 
 
 class DiscoCfg(C.Structure):
@@ -100,6 +102,9 @@ PROTOTYPES = {
     'disco_band_stats_gated': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _int, _vp, _vp]),
     'disco_pair_stats_spans': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
     'disco_band_stats_spans': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp]),
+    'disco_seg_snr': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _f, _f, _vp, _vp]),
+    'disco_rir_split': (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    'disco_reverb_energies': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     'disco_lag_corr_workspace_bytes': (_sz, [_vp, _i64, _i64, _int]),
     'disco_lag_corr': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _sz, _vp]),
     'disco_lag_corr_spans': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _int, _int, _vp, _vp, _sz, _vp]),

@@ -26,8 +26,11 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fno-slp-vectorize', '-f
 # accumulators in registers.  k_estoi_corr, k_estoi_finish (csrc/k_estoi.h): none -- a column's 2 x 15 float64 values stay in registers.
 # k_source_masks (csrc/k_stft.h): none -- the spectra of all talkers of a frame live in registers (the 1024-point plans of 5 to 8 talkers
 # lean on the accumulator half of the file: 76 and 144 copies).  k_source_mix: none -- the channel targets are read from the arguments.
+# k_reverb_mac_energy, k_reverb_spectra, k_rir_split (csrc/k_reverb.h): none -- the two accumulator sets of four output blocks are 144
+# registers with compile-time indices.  k_seg_snr (csrc/k_segsnr.h): none -- a window's 2 x 32 samples per lane stay in registers.
 SCRATCH_LIMIT = {'k_room_cov_dma': 64, 'k_gevd_mwf_r1_dpp': 0, 'k_apply_istft_wide': 0, 'k_gevd_full': 0, 'k_gevd_mwf_r1_wide': 0,
-                 'k_cov_wide': 0, 'k_estoi_corr': 0, 'k_estoi_finish': 0, 'k_source_masks': 0, 'k_source_mix': 0}
+                 'k_cov_wide': 0, 'k_estoi_corr': 0, 'k_estoi_finish': 0, 'k_source_masks': 0, 'k_source_mix': 0,
+                 'k_reverb_mac_energy': 0, 'k_reverb_spectra': 0, 'k_rir_split': 0, 'k_seg_snr': 0}
 # units whose kernels read other lanes' registers through DPP inside inline asm (csrc/dpp64.h): hipcc cannot see those reads, so
 # the two DPP hazards (a VALU write of the source within 2 wait states, an EXEC write within 5) are checked on the device
 # assembly of the unit (disco_amd/check_dpp_hazards.py) and a build with a hazard is refused

@@ -2,8 +2,8 @@
 dataset_generation/gen_disco/convolve_signals.py, dataset_generation/gen_meetit/convolve_signals.py and
 disco_theque/dataset_utils/post_generator.py, without files and without redraw loops)."""
 from .meetings import get_value_range, meeting_masks, meeting_rooms, simulate_meetings, sir_at_nodes, sir_valid
-from .rooms import mix_rooms, simulate_rooms, snr_at_mics
+from .rooms import mix_rooms, reverb_at_mics, simulate_rooms, snr_at_mics
 from .signals import noise_segments, ssn_segments, target_segments
 
-__all__ = ['snr_at_mics', 'simulate_rooms', 'mix_rooms', 'target_segments', 'noise_segments', 'ssn_segments',
+__all__ = ['snr_at_mics', 'simulate_rooms', 'mix_rooms', 'reverb_at_mics', 'target_segments', 'noise_segments', 'ssn_segments',
            'simulate_meetings', 'sir_at_nodes', 'sir_valid', 'get_value_range', 'meeting_rooms', 'meeting_masks']

@@ -3,6 +3,7 @@
     snr_at_mics      convolve_signals.py:170-213    SNR per microphone (fw_snr mean), per node, and the reference's node-to-node difference
     simulate_rooms   convolve_signals.py:255-273    R rooms at once: noise level, RIRs, images, image VADs, SNRs, the acceptance rule
     mix_rooms        post_generator.py:99-115       the mix at one drawn SNR per room
+    reverb_at_mics   metrics.py:176-208             how reverberant the rooms came out: DRR and SRR at every microphone
 
 The signals stay on the device between the steps (DevBuf); the figures (SNRs, flags) are NumPy.  Nothing is drawn and nothing is redrawn
 here: room geometry, source signals and SNRs are the caller's, and so is the loop that replaces the rooms `simulate_rooms` marks invalid.
@@ -95,6 +96,37 @@ def simulate_rooms(target_dry, noise_dry, room_dims, absorption, src_pos, mic_po
     valid = np.all(lo < snr_nodes, axis=-1) & np.all(snr_nodes < hi, axis=-1) & (min_delta_snr < snr_diff)
     return dict(images=images, rirs=rirs, image_vad=image_vad, noise_dry=dry[1], snr_images=snr_images, snr_nodes=snr_nodes,
                 snr_diff=snr_diff, valid=valid, noise_gain=np.array(gain, np.float64))
+
+
+def reverb_at_mics(dry, rirs, reverb_start=20, fs=16000):
+    """How reverberant the rooms of `simulate_rooms` came out: metrics.reverb_ratios (metrics.py:176-208) at every microphone.
+    dry (R, Ld) with rirs (R, n_mic, rir_len), or source-major dry (S, R, Ld) with rirs (S, R, n_mic, rir_len) -- the `rirs` of
+    simulate_rooms as they are; dry may also be a list of S (R, Ld) arrays, e.g. [target_dry, out['noise_dry']], which are copied into
+    one source-major block.  NumPy arrays, device tensors or DevBufs.
+    -> dict of NumPy arrays shaped like rirs without its last axis: drr, srr (dB) and split (the first tap of the tail, int32).
+    One Engine.rir_split and one Engine.reverb_energies call for all sources; neither convolution is written to memory."""
+    eng = _engine()
+    if isinstance(dry, (list, tuple)):
+        parts = [_dev(eng, d) for d in dry]
+        R, Ld = (int(v) for v in parts[0].shape)
+        block = eng.empty((len(parts), R, Ld), np.float32)
+        for i, d in enumerate(parts):
+            if tuple(int(v) for v in d.shape) != (R, Ld):
+                raise ValueError(f'every dry source must be ({R}, {Ld}): source {i} is {tuple(d.shape)}')
+            eng.mix_scaled(None, d, 1.0, n_out=block[i])              # gain 1 is exact: a copy
+        dry = block
+    dry, rirs = _dev(eng, dry), _dev(eng, rirs)
+    lead = tuple(int(v) for v in dry.shape[:-1])
+    if len(lead) not in (1, 2) or tuple(int(v) for v in rirs.shape[:len(lead)]) != lead or len(rirs.shape) != len(lead) + 2:
+        raise ValueError(f'dry must be (R, Ld) with rirs (R, n_mic, rir_len), or (S, R, Ld) with (S, R, n_mic, rir_len): '
+                         f'{tuple(dry.shape)} and {tuple(rirs.shape)}')
+    n_sig = int(np.prod(lead, dtype=np.int64))
+    n_mic, rir_len = int(rirs.shape[-2]), int(rirs.shape[-1])
+    h = rirs.reshape(n_sig, n_mic, rir_len)
+    split, e_h = eng.rir_split(h, int(1e-3 * reverb_start * fs))
+    e_x = eng.reverb_energies(dry.reshape(n_sig, int(dry.shape[-1])), h, split).numpy()
+    shape = lead + (n_mic,)
+    return dict(drr=metrics._ratio_db(e_h.numpy()).reshape(shape), srr=metrics._ratio_db(e_x).reshape(shape), split=split.numpy().reshape(shape))
 
 
 def mix_rooms(tar_img, noi_img, snr, mics_per_node, lengths=None):

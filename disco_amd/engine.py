@@ -549,6 +549,51 @@ class Engine:
             self._chk(self.lib.disco_band_stats(self.ctx, px, n_sig, L, start, stop, pb, pa, b.shape[0], st.ptr, self.stream))
         return st
 
+    def seg_snr(self, s, n, win_len, win_hop, vad=None, start=0, stop=None, lo_db=-15.0, hi_db=25.0):
+        """s, n (n_sig, L) float32, vad (n_sig, L) float32 or None -> (n_sig, 4) float64 {sum g v, sum g, N_w, #windows at a clip bound} of
+        the segmental SNR over [start, stop) (disco_seg_snr): v the clipped window level ratio in dB, g = 1 or vad[:, start + m win_hop].
+        stop: None (L), a scalar, or an (n_sig,) array -- nothing at or beyond stop[i] is read."""
+        if len(s.shape) != 2 or tuple(s.shape) != tuple(n.shape):
+            raise ValueError(f's and n must both be (n_sig, L): {tuple(s.shape)} and {tuple(n.shape)}')
+        n_sig, L = (int(v) for v in s.shape)
+        if vad is not None and tuple(vad.shape) != (n_sig, L):
+            raise ValueError(f'the VAD is indexed like the signals, {(n_sig, L)}: {tuple(vad.shape)}')
+        pst, kst = self._span_stops_dev(stop, n_sig, L, start, 'each')
+        ps, ks = self.to_device(s, np.float32)
+        pn, kn = self._alias(n, s, (ps, ks), np.float32, none='null')
+        pv, kv = self.to_device(vad, np.float32)
+        out = self.empty((n_sig, 4), np.float64)
+        self._chk(self.lib.disco_seg_snr(self.ctx, ps, pn, pv, n_sig, L, start, pst, win_len, win_hop, lo_db, hi_db, out.ptr, self.stream))
+        return out
+
+    # ---- how reverberant a room came out (metrics.py:176-208)
+    def rir_split(self, rir, n_direct):
+        """rir (..., rir_len) float32 -> (split (...,) int32, energy (..., 2) float64) as DevBufs: split = min(argmax + n_direct, rir_len),
+        energy = {sum rir[:split]^2, sum rir[split:]^2}  (disco_rir_split)."""
+        shape = tuple(int(v) for v in rir.shape)
+        n_rir = int(np.prod(shape[:-1], dtype=np.int64))
+        pr, kr = self.to_device(rir, np.float32)
+        split, energy = self.empty(shape[:-1], np.int32), self.empty(shape[:-1] + (2,), np.float64)
+        self._chk(self.lib.disco_rir_split(self.ctx, pr, n_rir, shape[-1], int(n_direct), split.ptr, energy.ptr, self.stream))
+        return split, energy
+
+    def reverb_energies(self, dry, rir, split):
+        """dry (n_sig, Ld), rir (n_sig, n_ch, rir_len) float32, split (n_sig, n_ch) int32 -> (n_sig, n_ch, 2) float64
+        {sum (dry * rir[:split])^2, sum (dry * rir[split:])^2} over the full convolutions, neither of which is written to memory
+        (disco_reverb_energies)."""
+        if len(dry.shape) != 2 or len(rir.shape) != 3 or int(rir.shape[0]) != int(dry.shape[0]):
+            raise ValueError(f'dry must be (n_sig, Ld) and rir (n_sig, n_ch, rir_len): {tuple(dry.shape)} and {tuple(rir.shape)}')
+        n_sig, Ld = (int(v) for v in dry.shape)
+        n_ch, Lh = int(rir.shape[1]), int(rir.shape[2])
+        if tuple(int(v) for v in split.shape) != (n_sig, n_ch):
+            raise ValueError(f'split must be {(n_sig, n_ch)}: {tuple(split.shape)}')
+        pd, kd = self.to_device(dry, np.float32)
+        pr, kr = self.to_device(rir, np.float32)
+        psp, ksp = self.to_device(split, np.int32)
+        energy = self.empty((n_sig, n_ch, 2), np.float64)
+        self._chk(self.lib.disco_reverb_energies(self.ctx, pd, pr, psp, n_sig, n_ch, Ld, Lh, energy.ptr, self.stream))
+        return energy
+
     def lag_corr(self, a, b, lag_lo, lag_hi, start=0, stop=None):
         """a, b (n_pair, L) float32 -> (n_pair, lag_hi - lag_lo + 1) float64: c[i][t - lag_lo] = sum_n a[i][n] b[i][n + t] over the n with
         n and n + t inside [start, stop); lags within +-511  (disco_lag_corr).  stop: None (L), a scalar, or an (n_pair,) array -- pair i

@@ -7,6 +7,10 @@ clipping / importance-weight arithmetic of the reference is applied to those.
 
     snr, delta_snr, sd        metrics.py:9-61       variance of the NON-ZERO samples, as the reference
     fw_snr, fw_sd             metrics.py:63-128, 211-279   (third-octave Butterworth bank, clip, band-importance weights)
+    seg_snr                   metrics.py:131-173      (clipped level ratio of every whole window, VAD-weighted; csrc/k_segsnr.h)
+    reverb_ratios             metrics.py:176-208      (DRR and SRR of dry signals through RIRs; csrc/k_reverb.h: the two convolutions
+                              are reduced to their energies without being written)
+    ci_wp                     metrics.py:283-288      (host NumPy on a handful of numbers; misc_utils.bar_data is its caller)
     si_sdr                    metrics.py:342-391
     si_bss                    metrics.py:282-340      (SI-SDR / SI-SIR / SI-SAR against n_src references)
     bss_eval_sources          mir_eval.separation.bss_eval_sources as tango.py:541-567 calls it (SDR / SIR / SAR through a 512-tap
@@ -95,6 +99,77 @@ def sd(s_out, s_in, db=True, start=0, stop=None):
     """metrics.py:48-61"""
     v = _levels(s_in, start, stop) / _levels(s_out, start, stop)
     return lin2db(v) if db else v
+
+
+def _as_signals(x):
+    """A NumPy array (or anything np.asarray takes) -> contiguous float32; a device tensor / DevBuf as it is."""
+    if isinstance(x, np.ndarray) or not (hasattr(x, 'data_ptr') or hasattr(x, 'ptr')):
+        return np.ascontiguousarray(x, dtype=np.float32)
+    return x
+
+
+def seg_snr(s, n, win_len, win_hop, vad=None, start=0, stop=None):
+    """metrics.py:131-173, batched over the leading axes: -> one value per signal pair in dB (a float for 1-D inputs).
+    Over the span [start, stop[i]) of L_i samples, windows m = 0 .. N_w - 1 cover [start + m win_hop, start + m win_hop + win_len) with
+    N_w = (L_i - win_len) // win_hop + 1 (whole windows only; none when L_i < win_len).  Per window and signal the variance is np.var in
+    float64 on the float32 samples, floored at sys.float_info.epsilon; v_m = clip(10 log10(var_s / var_n), -15, 25); the result is
+    sum g_m v_m / sum g_m with g_m = 1, or, with a VAD, g_m = vad[i][start + m win_hop] (the value itself, not a non-zero test).
+    vad is per SAMPLE and shaped like s: what sigproc_utils.vad_oracle_batch returns.  The reference takes one value per window from a
+    `db_utils.frame_vad` it does not ship; the decimation used here is the one the reference itself applies to a per-sample VAD for its
+    'ivad' masks (tango.py:219-220, vad[::N_HOP]).  The log, the clip and the sums happen in the kernel (Engine.seg_snr,
+    csrc/k_segsnr.h); two numbers per signal are divided here.
+    NaN where N_w = 0 or sum g_m = 0 (the reference divides by zero there).  s and n must have equal shapes: unequal shapes raise
+    ValueError -- the reference's reflect-padding of the shorter signal is not offered.  win_len <= 2048."""
+    s, n = _as_signals(s), _as_signals(n)
+    shape = tuple(int(v) for v in s.shape)
+    if len(shape) < 1 or tuple(int(v) for v in n.shape) != shape:
+        raise ValueError(f's and n must have the same shape, found {shape} and {tuple(n.shape)} (no reflect-padding of the shorter one here)')
+    if vad is not None:
+        vad = _as_signals(vad)
+        if tuple(int(v) for v in vad.shape) != shape:
+            raise ValueError(f'vad must be per sample and shaped like s, {shape}: found {tuple(vad.shape)}')
+    lead, L = shape[:-1], shape[-1]
+    n_sig = int(np.prod(lead, dtype=np.int64))
+    if L == 0 or n_sig == 0:                                     # nothing to read: no window anywhere
+        return np.full(lead, np.nan) if lead else float('nan')
+    flat = lambda a: a.reshape(n_sig, L)
+    st = _engine().seg_snr(flat(s), flat(n), int(win_len), int(win_hop), None if vad is None else flat(vad), int(start),
+                           _span_stops(stop, lead)).numpy()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        v = np.where(st[:, 2] > 0, st[:, 0] / st[:, 1], np.nan)
+    return v.reshape(lead) if lead else float(v[0])
+
+
+def reverb_ratios(x, rir, reverb_start=20, fs=16000):
+    """metrics.py:176-208, batched: x (n_sig, Ld) dry signals, rir (n_sig, n_ch, rir_len), rir_len <= 8192 -> (drr, srr) in dB, each
+    (n_sig, n_ch); a 1-D x with a 1-D rir (the reference's own call) -> two floats.
+        split = min(argmax(rir) + n_d, rir_len), n_d = int(1e-3 reverb_start fs)     (argmax of the signed response, first maximum)
+        h_d = rir[:split], h_r = rir[split:];  drr = 10 log10(sum h_d^2 / sum h_r^2);  srr = 10 log10(sum (x * h_d)^2 / sum (x * h_r)^2)
+    over the full convolutions, energies in float64 (Engine.rir_split, Engine.reverb_energies: csrc/k_reverb.h; neither convolution is
+    written to memory).  An empty tail (split == rir_len) gives +inf for both; the reference raises ValueError from np.convolve there,
+    which a batch cannot do for one of its rows."""
+    x, rir = _as_signals(x), _as_signals(rir)
+    one = len(x.shape) == 1 and len(rir.shape) == 1
+    if one:
+        x, rir = x.reshape(1, -1), rir.reshape(1, 1, -1)
+    if len(x.shape) != 2 or len(rir.shape) != 3 or int(rir.shape[0]) != int(x.shape[0]):
+        raise ValueError(f'x must be (n_sig, Ld) and rir (n_sig, n_ch, rir_len), or both 1-D: {tuple(x.shape)} and {tuple(rir.shape)}')
+    eng = _engine()
+    split, e_h = eng.rir_split(rir, int(1e-3 * reverb_start * fs))
+    e_x = eng.reverb_energies(x, rir, split).numpy()
+    drr, srr = _ratio_db(e_h.numpy()), _ratio_db(e_x)
+    return (float(drr[0, 0]), float(srr[0, 0])) if one else (drr, srr)
+
+
+def _ratio_db(e):
+    """(..., 2) energies -> 10 log10(e[..., 0] / e[..., 1]): +inf for an empty tail, -inf for an empty direct part, NaN for 0 / 0."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return 10 * np.log10(e[..., 0] / e[..., 1])
+
+
+def ci_wp(x, axis=0):
+    """metrics.py:283-288: the 95 % confidence half-width 1.96 nanstd(x) / sqrt(n) along `axis` (host NumPy, as the reference)."""
+    return 1.96 * np.nanstd(x, axis=axis) / np.sqrt(np.shape(x)[axis])
 
 
 def si_sdr(reference, estimation, start=0, stop=None):

@@ -92,10 +92,15 @@ STOI_KEYS = tuple(k for k in THIRD_PARTY_KEYS if 'stoi' in k)
 # as their delta_stoi* counterparts; without it the dictionaries, and so the pickles, keep the reference's key set.
 ESTOI_KEYS_TANGO = ('delta_estoi_cnv', 'delta_estoi_dry')
 ESTOI_KEYS_MWF = ('delta_estoi', 'delta_estoi_dry')
+# The segmental SNR (disco_amd.metrics.seg_snr) is not in the reference's pickles either: on `seg_snr=True` both dictionaries gain these two
+# keys -- the per-frame level figure the frequency-weighted SNR does not replace -- over windows of SEG_SNR_WINDOW samples of the scored span,
+# weighted by vad_oracle_batch of the target image cut to that span.
+SEG_SNR_KEYS = ('seg_snr_in_cnv', 'seg_snr_out')
+SEG_SNR_WINDOW = (512, 256)             # win_len, win_hop
 
 
 def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
-                 bss_flen=512, stoi=False, estoi=False):
+                 bss_flen=512, stoi=False, estoi=False, seg_snr=False):
     """The two result dictionaries of one (room, noise) (tango.py:541-635).
     s_in, n_in (K, L): target / noise images at every node's first microphone; sf_t, nf_t (K, L): their step-2 outputs in time;
     szf_t, nzf_t (K, L): their compressed (step-1) versions in time; rnd_snrs: the drawn input SNRs; s_dry, n_dry (L,): the dry
@@ -111,7 +116,10 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
     leaves those keys NaN.
     estoi=True: `res` gains `delta_estoi_cnv` and `delta_estoi_dry`, `resz` gains `delta_estoi` and `delta_estoi_dry` (ESTOI_KEYS_TANGO,
     ESTOI_KEYS_MWF), formed as their delta_stoi* counterparts from disco_amd.metrics.estoi on the same pairs; NaN without the three time
-    signals (the `_dry` ones without the dry sources).  The default adds no key."""
+    signals (the `_dry` ones without the dry sources).  The default adds no key.
+    seg_snr=True: both dictionaries gain `seg_snr_in_cnv` = metrics.seg_snr(s_in, n_in) and `seg_snr_out` -- of (sf_t, nf_t) in `res`, of
+    (szf_t, nzf_t) in `resz` (SEG_SNR_KEYS) -- over windows of 512 samples at hop 256 of the scored span [fs:], weighted by
+    vad_oracle_batch of the cut s_in.  The default adds no key and no call."""
     from .. import metrics as dm
     K = np.shape(s_in)[0]
     bss = y_in is not None and sh_t is not None and szh_t is not None
@@ -164,6 +172,12 @@ def room_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_d
     if estoi:
         for r, keys in ((res, ESTOI_KEYS_TANGO), (resz, ESTOI_KEYS_MWF)):
             r.update({k: nan.copy() for k in keys})
+    if seg_snr:
+        from .. import sigproc_utils as su
+        vad = su.vad_oracle_batch(cut(s_in))
+        seg = lambda s, n: np.asarray(dm.seg_snr(cut(s), cut(n), *SEG_SNR_WINDOW, vad=vad))
+        res['seg_snr_in_cnv'] = resz['seg_snr_in_cnv'] = seg(s_in, n_in)
+        res['seg_snr_out'], resz['seg_snr_out'] = seg(sf_t, nf_t), seg(szf_t, nzf_t)
     measures = [(nm, f) for nm, f, on in (('stoi', dm.stoi, stoi), ('estoi', dm.estoi, estoi)) if on and bss]
     if measures:                                                                           # the pairs are stacked once for both measures
         clean = [cut(s_in)] + ([np.repeat(cut(s_dry)[None], K, axis=0)] if s_dry is not None else [])
@@ -211,7 +225,7 @@ def _trim(a, L):
 
 
 def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_dry=None, fs=FS, y_in=None, sh_t=None, szh_t=None,
-                  bss_flen=512, stoi=False, lengths=None, estoi=False):
+                  bss_flen=512, stoi=False, lengths=None, estoi=False, seg_snr=False):
     """`room_results` for a whole batch of rooms, clips of different lengths included, in a handful of launches instead of one pass of
     Python per room: signals (R, K, L), dry sources (R, L), rnd_snrs (R, ...), as NumPy arrays (copied to the device) or -- all of them --
     device-resident torch tensors (read in place; no signal comes to the host).  lengths (R,): room r is scored over [fs, lengths[r]),
@@ -223,7 +237,9 @@ def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_
     Engine.BSS_WORKSPACE_BUDGET: a chunk's estimate sets are formed on the device (Engine.bss_estimates, 24 L bytes per node) and scored
     twice, against (s_in, n_in) per node and against the room's dry pair with 3 K estimate sets.  An all-zero reference raises
     ValueError naming the room and the node.  STOI: one Engine.stoi call for all 6 R K pairs, with a stop per pair; estoi=True: the
-    four ESTOI keys of `room_results` from one Engine.estoi call on the same pairs and stops."""
+    four ESTOI keys of `room_results` from one Engine.estoi call on the same pairs and stops.  seg_snr=True: the two segmental-SNR keys of
+    `room_results` (SEG_SNR_KEYS) in both dictionaries, from one Engine.vad_samples and three Engine.seg_snr calls on the signals cut to
+    [fs:], with a stop per (room, node)."""
     from .. import metrics as dm
     R, K = (int(v) for v in np.shape(s_in)[:2])
     bss = y_in is not None and sh_t is not None and szh_t is not None
@@ -328,6 +344,18 @@ def batch_results(s_in, n_in, sf_t, nf_t, szf_t, nzf_t, rnd_snrs, s_dry=None, n_
     if estoi:
         for r, keys in ((res, ESTOI_KEYS_TANGO), (resz, ESTOI_KEYS_MWF)):
             r.update({k: nan.copy() for k in keys})
+    if seg_snr:
+        cut = lambda a: (np.ascontiguousarray(a[..., fs:Lmin]) if host else a[..., fs:Lmin].contiguous()).reshape(R * K, Lmin - fs)
+        stops = (stop_rk - fs).astype(np.int32)
+        vad = eng.vad_samples(cut(sig['s_in']), stop=stops)
+
+        def seg(s, n):
+            st = eng.seg_snr(cut(sig[s]), cut(sig[n]), *SEG_SNR_WINDOW, vad=vad, stop=stops).numpy()
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return np.where(st[:, 2] > 0, st[:, 0] / st[:, 1], np.nan).reshape(R, K)
+
+        res['seg_snr_in_cnv'] = resz['seg_snr_in_cnv'] = seg('s_in', 'n_in')
+        res['seg_snr_out'], resz['seg_snr_out'] = seg('sf_t', 'nf_t'), seg('szf_t', 'nzf_t')
     measures = [(nm, f) for nm, f, on in (('stoi', eng.stoi, stoi), ('estoi', eng.estoi, estoi)) if on and bss]
     if measures:                                                                          # the pairs are stacked once for both measures
         Ls = Lr

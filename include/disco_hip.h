@@ -566,6 +566,23 @@ int disco_band_stats_gated(disco_ctx* ctx, const float* x, const float* gate, in
 int disco_band_stats_spans(disco_ctx* ctx, const float* x, const float* gate, int64_t n_sig, int64_t len, int start, const int32_t* stop,
                            const double* b, const double* a, int n_bands, double* stats, disco_stream s);
 
+/* disco_seg_snr: the segmental SNR of disco_theque/metrics.py:131-173 for n_sig signal pairs s, n [n_sig][len] float.  Pair i is scored
+ * over [start, stop[i]) (stop: device array of n_sig int32, clamped into [start, len]; NULL = len) as if sliced and scored alone; nothing
+ * at or beyond stop[i] is read.  With L = stop[i] - start: windows m = 0 .. N_w - 1 cover [start + m win_hop, start + m win_hop + win_len),
+ * N_w = (L - win_len) / win_hop + 1, 0 when L < win_len (whole windows only).  Per window and signal, in float64 on the float32 samples:
+ * mean = sum x / win_len, var = sum (x - mean)^2 / win_len (two passes, as np.var), floored at 2.220446049250313e-16;
+ * v_m = clip(10 log10(var_s / var_n), lo_db, hi_db); weight g_m = 1, or vad[i][start + m win_hop] with vad [n_sig][len] float (the value
+ * itself, not a non-zero test).
+ *   out[i][4] = { sum g_m v_m, sum g_m, N_w, number of windows with v_m at a clip bound }
+ * The segmental SNR sum g v / sum g is host arithmetic.  One workgroup per pair: row i has the same bits whatever else is in the batch
+ * and from run to run, and a NaN inside row i changes no bit of any other row.
+ * DISCO_E_ARG, nothing written: win_len < 1, win_hop < 1, win_hop > win_len, lo_db >= hi_db, a null s, n or out, n_sig < 0, start outside
+ * [0, len].  DISCO_E_UNSUPPORTED: win_len > DISCO_SEG_SNR_MAX_WIN (a wave keeps a window of both signals in registers between the two
+ * passes), len > 2^31 - 1. */
+#define DISCO_SEG_SNR_MAX_WIN 2048
+int disco_seg_snr(disco_ctx* ctx, const float* s, const float* n, const float* vad, int64_t n_sig, int64_t len, int start,
+                  const int32_t* stop, int win_len, int win_hop, float lo_db, float hi_db, double* out, disco_stream st);
+
 /* ---- BSS-eval SDR / SIR / SAR (what tango.py:541-567 takes from mir_eval.separation.bss_eval_sources) ---------------
  * Restated from its definition (Vincent, Gribonval, Fevotte 2006): the estimate is projected on the flen delayed copies of
  * the target reference and on those of all nsrc references; every figure is a function of lag correlations only.
@@ -669,6 +686,27 @@ int disco_estoi_bands(disco_ctx* ctx, const float* tob_x, const float* tob_y, in
  * Partitioned overlap-save with 1024-point wave FFTs; the spectra workspace lives in the context. */
 int disco_rir_convolve(disco_ctx* ctx, const float* dry, const float* rir, int64_t n_sig, int n_ch,
                        int dry_len, int rir_len, float* out, int out_len, disco_stream s);
+
+/* ---- how reverberant a room came out: DRR and SRR (disco_theque/metrics.py:176-208) -------------------------------------------
+ * disco_rir_split: for each of n_rir impulse responses rir [n_rir][rir_len] float,
+ *   split[i] = min(argmax(rir[i]) + n_direct, rir_len)   (int32; np.argmax of the SIGNED response: the first of equal maxima, and a NaN
+ *   wins at its first index);  energy[i][2] = { sum rir[i][:split]^2, sum rir[i][split:]^2 } in float64 (the squares are exact), added
+ *   in a fixed order.  DRR = 10 log10(energy[0] / energy[1]) is host arithmetic.  One workgroup per response: a NaN stays in its row.
+ * DISCO_E_ARG, nothing written: a null pointer, n_rir < 0, rir_len < 1, n_direct < 0.  DISCO_E_UNSUPPORTED: rir_len > 8192.
+ *
+ * disco_reverb_energies: dry [n_sig][dry_len], rir [n_sig][n_ch][rir_len], split [n_sig][n_ch] int32 (device memory; a value outside
+ * [0, rir_len] is clamped into it) ->
+ *   energy[i][c][2] = { sum np.convolve(dry[i], rir[i][c][:split])^2, sum np.convolve(dry[i], rir[i][c][split:])^2 }   (float64)
+ * over the FULL convolutions (dry_len + rir_len - 1 samples); an empty side gives an exact 0.  SRR = 10 log10(energy[0] / energy[1]).
+ * The partitioned overlap-save of disco_rir_convolve (its arithmetic, its spectra workspace in the context) with two accumulator sets
+ * per output block and no output store: neither convolution is written to memory, and neither is formed as a difference.  A row's bits
+ * depend on nothing else in the batch, and a NaN in one response or one dry signal reaches only its own rows.
+ * DISCO_E_ARG, nothing written: a null pointer, n_sig < 0, n_ch < 1, dry_len < 1, rir_len < 1.  DISCO_E_UNSUPPORTED: rir_len > 8192. */
+#define DISCO_REVERB_MAX_RIR 8192
+int disco_rir_split(disco_ctx* ctx, const float* rir, int64_t n_rir, int rir_len, int n_direct, int32_t* split, double* energy,
+                    disco_stream s);
+int disco_reverb_energies(disco_ctx* ctx, const float* dry, const float* rir, const int32_t* split, int64_t n_sig, int n_ch, int dry_len,
+                          int rir_len, double* energy, disco_stream s);
 
 /* Shoebox image-source room impulse responses -- what the reference takes from pyroomacoustics
  * (dataset_generation/gen_disco/convolve_signals.py:243-246 pra.ShoeBox(dims, fs, max_order=20, absorption); :94-95
