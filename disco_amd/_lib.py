@@ -18,7 +18,8 @@ FLAG_LAZY_SCRATCH = 2
 FLAG_NO_CHILDREN = 4
 SEG_SNR_MAX_WIN = 2048                  # DISCO_SEG_SNR_MAX_WIN: the longest window disco_seg_snr takes
 REVERB_MAX_RIR = 8192                   # DISCO_REVERB_MAX_RIR: the longest response disco_rir_split / disco_reverb_energies take
-ESTOI_SEGS = 64                 # DISCO_ESTOI_SEGS of include/disco_hip.h: segments one workgroup of k_estoi_corr owns
+RECON_LOSS_WS_BYTES = 16384             # DISCO_RECON_LOSS_WS_BYTES: the workspace disco_recon_loss never needs more than
+ESTOI_SEGS = 64                # DISCO_ESTOI_SEGS of include/disco_hip.h: segments one workgroup of k_estoi_corr owns
 
 
 class DiscoCfg(C.Structure):
@@ -90,6 +91,11 @@ PROTOTYPES = {
     'disco_noise_from_signal': (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     'disco_affine_segment': (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp]),
     'disco_gru_gates':(_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    'disco_gru_gates_train': (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    'disco_gru_gates_backward': (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp]),
+    'disco_recon_loss': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _sz, _vp]),
+    'disco_recon_loss_grad': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    'disco_train_batch': (_int, [_vp, _vp, _int, _i64, _int, _int, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     'disco_maxpool_last4': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     'disco_conv3x3_pool4': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
     'disco_crnn_features': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, C.c_float, C.c_float, _vp, _vp]),
@@ -146,11 +152,19 @@ def bind(cdll):
 
 
 _lib = None
+_gfx950 = None      # what load() itself opened: the only library the package ever loads
+
+
+def takes_host_memory():
+    """True where a test has put a library of its own in `_lib` (the hipemu build, whose "device" pointers are host pointers).  The training
+    wrappers (dnn/losses.py, dnn/crnn.py) then drive their kernels on CPU tensors too; with the gfx950 library, or none, CPU tensors take the
+    torch expressions."""
+    return _lib is not None and _lib is not _gfx950
 
 
 def load():
     """Load the gfx950 library.  Fails loudly -- there is no other implementation to fall back to."""
-    global _lib
+    global _lib, _gfx950
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
@@ -164,5 +178,5 @@ def load():
             import torch  # noqa: F401
         except ImportError:
             pass
-        _lib = bind(C.CDLL(LIB_PATH))
+        _lib = _gfx950 = bind(C.CDLL(LIB_PATH))
     return _lib

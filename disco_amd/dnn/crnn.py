@@ -198,6 +198,133 @@ def _crnn_expand_rows_hip(rows, B, T, frames_sig, row0):
     return out
 
 
+# ---- training: the recurrent layer as GEMMs + the gate kernels, under autograd ---------------------------------------------------------------
+
+def _stream_of(t):
+    """The stream a kernel for tensor `t` goes to: the current one of t's device; 0 for a CPU tensor (a test driving the emulated library)."""
+    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
+
+
+class _DeviceOf:
+    """`with _DeviceOf(t):` -- torch.cuda.device(t.device) for a GPU tensor, nothing for a CPU tensor."""
+
+    def __init__(self, t):
+        self.ctx = torch.cuda.device(t.device) if t.is_cuda else None
+
+    def __enter__(self):
+        if self.ctx is not None:
+            self.ctx.__enter__()
+
+    def __exit__(self, *exc):
+        if self.ctx is not None:
+            self.ctx.__exit__(*exc)
+
+
+def _use_kernels(t):
+    """A GPU tensor always goes through the kernels (float32 only; a missing library is an error, not a fall-back).  A CPU tensor takes the
+    same formulas in torch ops, unless a test has bound the emulated build by hand (_lib.takes_host_memory)."""
+    from .. import _lib
+    if t.is_cuda:
+        if t.dtype != torch.float32:
+            raise TypeError(f'the training kernels are float32, got {t.dtype}')
+        return True
+    return t.dtype == torch.float32 and _lib.takes_host_memory()
+
+
+def _gru_step_train(g, gh, b_hh, h_prev, h_out, saved, kernels):
+    """One forward step that keeps saved = [r | z | c | gh_n] (disco_gru_gates_train, or the same arithmetic in torch ops)."""
+    n, H = h_out.shape
+    if kernels:
+        from .. import _lib
+        assert g.stride(1) == 1 and (gh is None or gh.is_contiguous()) and h_out.is_contiguous() and saved.is_contiguous()
+        with _DeviceOf(g):
+            rc = _lib.load().disco_gru_gates_train(None, g.data_ptr(), g.stride(0), None if gh is None else gh.data_ptr(), b_hh.data_ptr(),
+                                                   None if h_prev is None else h_prev.data_ptr(), h_out.data_ptr(), saved.data_ptr(), n, H,
+                                                   _stream_of(g))
+        if rc != 0:
+            raise RuntimeError(f'disco_gru_gates_train failed ({rc})')
+        return
+    gh = b_hh.expand(n, -1) if gh is None else gh
+    r = torch.sigmoid(g[:, :H] + gh[:, :H])
+    z = torch.sigmoid(g[:, H:2 * H] + gh[:, H:2 * H])
+    c = torch.tanh(g[:, 2 * H:] + r * gh[:, 2 * H:])
+    h_out.copy_((1 - z) * c if h_prev is None else (1 - z) * c + z * h_prev)
+    saved.copy_(torch.cat((r, z, c, gh[:, 2 * H:]), 1))
+
+
+def _gru_step_backward(d_out, d_carry, saved, h_prev, d_gi, d_gh, d_h, kernels):
+    """One step of back-propagation through time (disco_gru_gates_backward, or the same arithmetic in torch ops): d_gi (a strided slice of
+    the all-steps buffer), d_gh and d_h are written."""
+    n, H = d_h.shape
+    if kernels:
+        from .. import _lib
+        assert (d_out is None or d_out.stride(1) == 1) and (d_carry is None or d_carry.is_contiguous()) and d_gi.stride(1) == 1
+        with _DeviceOf(saved):
+            rc = _lib.load().disco_gru_gates_backward(None, None if d_out is None else d_out.data_ptr(), 0 if d_out is None else d_out.stride(0),
+                                                      None if d_carry is None else d_carry.data_ptr(), saved.data_ptr(),
+                                                      None if h_prev is None else h_prev.data_ptr(), d_gi.data_ptr(), d_gi.stride(0),
+                                                      d_gh.data_ptr(), d_h.data_ptr(), n, H, _stream_of(saved))
+        if rc != 0:
+            raise RuntimeError(f'disco_gru_gates_backward failed ({rc})')
+        return
+    d = d_carry if d_out is None else (d_out if d_carry is None else d_out + d_carry)
+    r, z, c, ghn = saved[:, :H], saved[:, H:2 * H], saved[:, 2 * H:3 * H], saved[:, 3 * H:]
+    dn = d * (1 - z)
+    dz = d * ((0 if h_prev is None else h_prev) - c)
+    da_n = dn * (1 - c * c)
+    da_z = dz * z * (1 - z)
+    da_r = da_n * ghn * r * (1 - r)
+    d_h.copy_(d * z)
+    d_gi.copy_(torch.cat((da_r, da_z, da_n), 1))
+    d_gh.copy_(torch.cat((da_r, da_z, da_n * r), 1))
+
+
+class _GruTrain(torch.autograd.Function):
+    """The one-layer GRU from a zero state over the leading `steps` steps of every sequence, as GEMMs plus the gate kernels; returns the
+    hidden states of steps ff_out ... steps - 1 as (steps - ff_out, n, H) -- the loss frames, the only ones anything downstream reads.
+    forward:  one GEMM for the input projections of all steps, then one recurrent GEMM + one disco_gru_gates_train per step.
+    backward: one disco_gru_gates_backward per step in reverse order, with carry = d_h_direct + d_gh W_hh; the weight gradients are then
+              single GEMMs over all steps at once: dW_hh = sum_t d_gh_t^T h_{t-1}, db_hh = sum_t d_gh_t, dW_ih, db_ih and dx from the
+              (n steps, 3H) buffer of d_gi."""
+
+    @staticmethod
+    def forward(ctx, seq, w_ih, w_hh, b_ih, b_hh, ff_out):
+        n, steps, n_in = seq.shape
+        H = w_hh.shape[1]
+        kernels = _use_kernels(seq)
+        seq2 = seq.reshape(n * steps, n_in)
+        gi = torch.addmm(b_ih, seq2, w_ih.t()).view(n, steps, 3 * H)
+        hs = torch.empty((steps, n, H), dtype=seq.dtype, device=seq.device)
+        saved = torch.empty((steps, n, 4 * H), dtype=seq.dtype, device=seq.device)
+        b_hh = b_hh.contiguous()
+        for t in range(steps):
+            gh = None if t == 0 else torch.addmm(b_hh, hs[t - 1], w_hh.t())
+            _gru_step_train(gi[:, t], gh, b_hh, None if t == 0 else hs[t - 1], hs[t], saved[t], kernels)
+        ctx.save_for_backward(seq2, w_ih, w_hh, hs, saved)
+        ctx.shape, ctx.ff_out, ctx.kernels = (n, steps, n_in), ff_out, kernels
+        return hs[ff_out:].clone()
+
+    @staticmethod
+    def backward(ctx, d_hs):
+        seq2, w_ih, w_hh, hs, saved = ctx.saved_tensors
+        (n, steps, n_in), ff_out, kernels = ctx.shape, ctx.ff_out, ctx.kernels
+        H = w_hh.shape[1]
+        d_hs = d_hs.contiguous()
+        d_gi = torch.empty((n, steps, 3 * H), dtype=hs.dtype, device=hs.device)
+        d_gh = torch.empty((steps, n, 3 * H), dtype=hs.dtype, device=hs.device)
+        carry = None
+        for t in range(steps - 1, -1, -1):
+            d_h = torch.empty((n, H), dtype=hs.dtype, device=hs.device)
+            _gru_step_backward(d_hs[t - ff_out] if t >= ff_out else None, carry, saved[t], None if t == 0 else hs[t - 1], d_gi[:, t], d_gh[t], d_h,
+                               kernels)
+            if t > 0:
+                carry = torch.addmm(d_h, d_gh[t], w_hh)
+        d_gi2 = d_gi.view(n * steps, 3 * H)
+        d_w_hh = d_gh[1:].reshape(-1, 3 * H).t() @ hs[:-1].reshape(-1, H) if steps > 1 else torch.zeros_like(w_hh)
+        d_seq = (d_gi2 @ w_ih).view(n, steps, n_in) if ctx.needs_input_grad[0] else None
+        return d_seq, d_gi2.t() @ seq2, d_w_hh, d_gi2.sum(0), d_gh.sum((0, 1)), None
+
+
 class _Seq(nn.Module):
     """Holder that reproduces the reference's `<brick>.model = nn.Sequential(...)` key layout."""
 
@@ -255,6 +382,44 @@ class CRNN(nn.Module):
         x = x.view(x.size(0), x.size(2), x.size(1) * x.size(-1))    # NB: a re-interpretation, not a transpose (crnn.py:59)
         x = self.rnn(x)
         return self.ff(x.squeeze())
+
+    def get_loss_frames(self, output_frames):
+        """((first, last + 1) of the INPUT / label frames, (first, last + 1) of the OUTPUT frames) that the loss compares for
+        'all' / 'mid' / 'last' (crnn.py:65-87): the convolutions drop 3 frames at either end of the 21."""
+        from .utils import get_loss_frames
+        win_len_in, win_len_out = self.input_shape[1], self.x_out
+        if output_frames == 'last':
+            ff_in = (win_len_in + win_len_out) // 2 - 1
+            lf_in = ff_in + 1
+        elif output_frames == 'mid':
+            ff_in = int(np.ceil(win_len_in) / 2)
+            lf_in = ff_in + 1
+        elif output_frames == 'all':
+            ff_in = (win_len_in - win_len_out) // 2
+            lf_in = (win_len_in + win_len_out) // 2
+        else:
+            raise ValueError("Unknown argument value {}. It should be either 'all', 'mid' or 'last'.".format(output_frames))
+        return (ff_in, lf_in), get_loss_frames(win_len_out, output_frames)
+
+    # ---- the training route (dnn/train.py): the recurrent layer through the gate kernels, the output layer on the loss frames only
+    def forward_train(self, x, output_frames='all'):
+        """x (B, n_ch, 21, F) or (B, 21, F) -> (B, n_out, F): `forward(x)[:, ff_out:lf_out]` for the output frames of
+        get_loss_frames(output_frames), differentiable, at a fraction of nn.GRU's cost on this shape.
+        The convolution / BatchNorm / pooling modules are the same ones `forward` runs, under autograd: in train mode that is batch
+        statistics, with the running statistics updated once per call exactly as `forward` updates them.  The reference's `.view`
+        (crnn.py:59) follows.  The GRU is run as GEMMs plus the gate kernels (_GruTrain) over the steps up to the last loss frame only
+        -- 8 for 'mid', 15 for 'all' and 'last' -- and the output layer and sigmoid on the loss frames only.
+        There is no dropout to restate: the reference gives its RNN brick rnn_dropouts = 0.5 but builds the one-layer GRU with
+        dropouts[-1] = 0 (nn_structures.py:124-126).
+        CPU tensors take the same formulas in torch ops."""
+        if x.dim() == 3:
+            x = x.view(x.size(0), 1, x.size(1), x.size(2))
+        f = self.cnn(x)
+        f = f.view(f.size(0), f.size(2), f.size(1) * f.size(-1))    # NB: a re-interpretation, not a transpose (crnn.py:59)
+        ff_out, lf_out = self.get_loss_frames(output_frames)[1]
+        gru = self.rnn.model[0].rnn_layer
+        hs = _GruTrain.apply(f[:, :lf_out], gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0, ff_out)      # (n_out, B, H)
+        return self.ff(hs).permute(1, 0, 2)
 
     def mid_frame(self):
         """Index of the output frame reshape_mask('mid') selects (tango.py:232-234)."""

@@ -485,6 +485,52 @@ int disco_tango_online_stream(disco_ctx* ctx, const float* y_new, int n_hops, co
 int disco_gru_gates(disco_ctx* ctx, const float* gi, int64_t gi_stride, const float* gh, const float* gh_bias,
                     const float* h_prev, float* h_out, int64_t n, int H, disco_stream s);
 
+/* ---- training the mask estimators (disco_amd/dnn/train.py; the reference's dnn/engine/train.py, dnn/utils.py:189-294, dnn/engine/losses.py,
+ * dnn/data/datasets.py).  The convolutions, BatchNorm, the GEMMs and the optimiser stay in PyTorch-ROCm with its autograd; these five are the
+ * recurrent layer's pointwise forward and backward, the loss with its gradient, and the batch gather.  ctx may be NULL in all of them.
+ *
+ * disco_gru_gates that also keeps what back-propagation needs: saved [n][4H] = [r | z | c | gh_n] (gh_n: the recurrent pre-activation of the
+ * candidate gate, the value r multiplies; gh_bias's third block on the first step).  h_out holds the bits disco_gru_gates writes. */
+int disco_gru_gates_train(disco_ctx* ctx, const float* gi, int64_t gi_stride, const float* gh, const float* gh_bias, const float* h_prev,
+                          float* h_out, float* saved, int64_t n, int H, disco_stream s);
+
+/* One step of back-propagation through time through disco_gru_gates_train.  With d = d_out + d_carry:
+ *   dn = d (1 - z),  dz = d (h_prev - c),  d_h_direct = d z,  da_n = dn (1 - c^2),  da_z = dz z (1 - z),  da_r = da_n gh_n r (1 - r)
+ *   d_out      rows of H floats at stride d_out_stride, or NULL: the gradient arriving at this step's output
+ *   d_carry    [n][H] or NULL: the gradient carried from step t + 1 (not both NULL)
+ *   saved      [n][4H] of this step;  h_prev [n][H] or NULL (= 0)
+ *   d_gi       = [da_r | da_z | da_n], rows of 3H floats at stride d_gi_stride (a step's slice of an [n][steps][3H] buffer)
+ *   d_gh       = [da_r | da_z | da_n r], [n][3H];  d_h_direct [n][H]
+ * The caller's GEMMs finish the step: d_carry' = d_h_direct + d_gh W_hh, dW_hh += d_gh^T h_prev, db_hh += sum_rows d_gh. */
+int disco_gru_gates_backward(disco_ctx* ctx, const float* d_out, int64_t d_out_stride, const float* d_carry, const float* saved,
+                             const float* h_prev, float* d_gi, int64_t d_gi_stride, float* d_gh, float* d_h_direct, int64_t n, int H,
+                             disco_stream s);
+
+/* reconstruction_loss (dnn/engine/losses.py:4-25) on the frames get_x_for_loss selects (dnn/utils.py:212-246), without slicing them out:
+ *   term(b, j, f) = ((est[b][j][f] - y[b][ff_in + j][f]) x[b][0][ff_in + j][f])^2,  j < n_out, ff_in + n_out <= W
+ * est [B][n_out][F], label y [B][W][F], input x [B][C][W][F] (channel 0 weights the loss), all float32.  Every term is formed and summed in
+ * float64; sums (device) receives {sum of the non-NaN terms, their count}, the loss is their quotient.  The order of summation is a function
+ * of B n_out F alone (per-workgroup partial sums in `workspace`, one fold, no atomics): two calls give the same bits.
+ * workspace: device memory, 8-byte aligned, DISCO_RECON_LOSS_WS_BYTES are always enough. */
+#define DISCO_RECON_LOSS_MAX_BLOCKS 1024
+#define DISCO_RECON_LOSS_WS_BYTES 16384
+int disco_recon_loss(disco_ctx* ctx, const float* est, const float* y, const float* x, int64_t B, int C, int W, int F, int ff_in, int n_out,
+                     double* sums, void* workspace, size_t workspace_bytes, disco_stream s);
+
+/* Its gradient: d_est[b][j][f] = g 2 (est - y) x^2 / count, formed in float64 and rounded once to float32; g (the upstream gradient, one
+ * float) and sums (what disco_recon_loss wrote) are read from device memory.  Exact +0 where the term is NaN -- the reference's autograd
+ * leaves 0 x NaN = NaN there. */
+int disco_recon_loss_grad(disco_ctx* ctx, const float* est, const float* y, const float* x, int64_t B, int C, int W, int F, int ff_in, int n_out,
+                          const double* sums, const float* g, float* d_est, disco_stream s);
+
+/* A training batch out of the spectra bank (DiscoDataset.get_subwindow, dnn/data/datasets.py:120-162): bank [S][N][T][F] float32 magnitudes (S
+ * signal rows, N segments), tab (device) [B][C + 3] int32 = per item (segment k, first frame m, C input rows, label row) ->
+ *   x[b][c] = bank[tab[b][2 + c]][k][m : m + W],  y[b] = bank[tab[b][2 + C]][k][m : m + W];   x [B][C][W][F], y [B][W][F].
+ * tab_host: the caller's host copy of tab, or NULL.  Given, every entry is checked before the launch and an entry out of range (segment, m + W > T,
+ * signal row) is DISCO_E_ARG.  The kernel itself never reads outside the bank: an item with such an entry comes out as zeros. */
+int disco_train_batch(disco_ctx* ctx, const float* bank, int S, int64_t N, int T, int F, const int32_t* tab, const int32_t* tab_host, int64_t B,
+                      int C, int W, float* x, float* y, disco_stream s);
+
 /* MaxPool2d((1, 4)) of the CRNN's convolutional stack (dnn/models/crnn.py via nn_structures.py): floor-mode maximum over groups
  * of 4 along the last axis, plus the preceding convolution's per-channel bias (a constant commutes with the maximum; adding it here
  * spares a pass over the four times larger un-pooled map).  x [B][channels][rows_per_channel][row_len] seen as n_rows rows ->
