@@ -96,6 +96,7 @@ PROTOTYPES = {
     'disco_recon_loss': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _sz, _vp]),
     'disco_recon_loss_grad': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     'disco_train_batch': (_int, [_vp, _vp, _int, _i64, _int, _int, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    'disco_bank_fill': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _int, _i64, _vp]),
     'disco_maxpool_last4': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     'disco_conv3x3_pool4': (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp]),
     'disco_crnn_features': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, C.c_float, C.c_float, _vp, _vp]),

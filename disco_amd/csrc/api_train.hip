@@ -7,17 +7,7 @@ using namespace disco_host;
 
 static_assert(TRAIN_LOSS_THREADS == 256 && DISCO_RECON_LOSS_MAX_BLOCKS * 16 == DISCO_RECON_LOSS_WS_BYTES, "header and kernel disagree");
 
-// ctx may be NULL in every entry point of this unit (the DNN owns no context): the launch then goes to the calling thread's current device
-static inline int current_device(const disco_ctx* ctx) {
-    if (ctx) return ctx->cfg.device;
-    int d = 0;
-    (void)hipGetDevice(&d);
-    return d;
-}
-static inline int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
-}
+// ctx may be NULL in every entry point of this unit (the DNN owns no context): current_device / launched of host.h
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static inline unsigned gate_grid(long long items) { return (unsigned)std::min<long long>((items + 255) / 256, 65536); }
 

@@ -40,6 +40,11 @@ __device__ __forceinline__ c32 cconj(c32 a) { return make_float2(a.x, -a.y); }
 __device__ __forceinline__ c32 cmul_mi(c32 a) { return make_float2(a.y, -a.x); }
 __device__ __forceinline__ c32 cmul_pi(c32 a) { return make_float2(-a.y, a.x); }
 
+// |a| as the CRNN's features and the training bank take it (k_crnn_conv.h crnn_feature_at, k_bank.h): ONE expression, so that what the network
+// sees in training is bit for bit what it sees at inference.  |a|^2 with its fma written out: hipcc's contraction chose
+// fma(a.x, a.x, a.y a.y) for the plain sum of squares, but its choice follows the code around it.  NaN passes.
+__device__ __forceinline__ float cabs_fma(c32 a) { return sqrtf(fmaf(a.x, a.x, a.y * a.y)); }
+
 __device__ __forceinline__ c64 zmul(c64 a, c64 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 // a * conj(b)
 __device__ __forceinline__ c64 zmulc(c64 a, c64 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }

@@ -162,7 +162,19 @@ struct DevGuard {
     DevGuard(const DevGuard&) = delete;
     DevGuard& operator=(const DevGuard&) = delete;
 };
-#define DISCO_ENTER(ctx)                                                                             \
+// Entry points whose ctx may be NULL (the DNN's helpers and the training bank own no context): the launch then goes to the calling thread's
+// current device, and a failed launch is reported by its code alone.
+static inline int current_device(const disco_ctx* ctx) {
+    if (ctx) return ctx->cfg.device;
+    int d = 0;
+    (void)hipGetDevice(&d);
+    return d;
+}
+static inline int launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : DISCO_E_HIP_BASE - (int)e;
+}
+#define DISCO_ENTER(ctx)                                                                        \
     if (!(ctx)) return DISCO_E_ARG;                                                                  \
     DevGuard dev_guard_((ctx)->cfg.device);                                                          \
     if (!dev_guard_.ok) return fail((ctx), DISCO_E_HIP_BASE, "hipSetDevice(cfg.device) failed")

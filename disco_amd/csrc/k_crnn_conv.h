@@ -86,8 +86,7 @@ static __device__ __forceinline__ float crnn_feature_at(const c32* __restrict__ 
         const int k = (int)(g % K), j = (c - 1) < k ? (c - 1) : c;            // the (c - 1)-th node other than k
         a = Z[(((g / K) * K + j) * T + t) * (long long)F + f];
     }
-    // |a|^2 with its fma written out: hipcc's contraction chose fma(a.x, a.x, a.y a.y) here, but its choice follows the code around it
-    const float m = sqrtf(fmaf(a.x, a.x, a.y * a.y));
+    const float m = cabs_fma(a);
     return m != m ? m : fminf(fmaxf(m, lo), hi);     // NaN passes, as np.clip / torch.clamp leave it (fmaxf would make it lo)
 }
 

@@ -214,7 +214,7 @@ def main(argv=None):
     p.add_argument('--batch-size', type=int, default=500)
     args = p.parse_args(argv)
     if not args.time_step:
-        p.error('nothing to do: --time-step (training itself is driven from Python: load_architecture, SpectraBank.from_files, fit)')
+        p.error('nothing to do: --time-step (training itself is driven from Python: load_architecture, SpectraBank.from_rooms or .from_files, fit)')
     for rec in time_step(steps=args.steps, rounds=args.rounds, batch_size=args.batch_size):
         print(json.dumps(rec))
 

@@ -531,6 +531,20 @@ int disco_recon_loss_grad(disco_ctx* ctx, const float* est, const float* y, cons
 int disco_train_batch(disco_ctx* ctx, const float* bank, int S, int64_t N, int T, int F, const int32_t* tab, const int32_t* tab_host, int64_t B,
                       int C, int W, float* x, float* y, disco_stream s);
 
+/* The spectra bank filled from rooms without leaving the device: the rows of bank [S][N][Tb][F] (float32, what disco_train_batch reads) of the R
+ * consecutive segments seg0 ... seg0 + R - 1, in one launch.  Sources, all on the device:
+ *   X       [R][K][T][F][M] complex64 mixture spectra, read at microphone `mic` (M = 1: the plain [R][K][T][F])
+ *   z0, z1  [R][K][T][F] complex64 compressed signals; either may be NULL, n_zsig is the number present (they keep their order)
+ *   mask    [R][K][T][F] float32 labels;  frames [R] int32 or NULL (= T for every room; a value above T counts as T)
+ * Rows (S = K (2 + n_zsig)): row k = |X| of node k, row K (1 + i) + k = |z signal i| of node k, row K (1 + n_zsig) + k = the mask of node k.
+ * Frame tb of segment seg0 + r holds source frame tb + skip while tb + skip < min(frames[r], T) and an exact +0 for every other tb < Tb: all Tb
+ * frames of the R segments are written, no other segment is touched, nothing is read out of range.  Magnitudes are
+ * sqrtf(fmaf(re, re, im * im)), the bits disco_crnn_features gives before its clip (NaN passes); mask values are copied bit for bit.
+ * DISCO_E_ARG, before anything is launched: X, mask or bank NULL, mic outside [0, M), skip < 0, Tb < 1, seg0 < 0, seg0 + R > N, n_zsig not
+ * the number of z pointers.  ctx may be NULL. */
+int disco_bank_fill(disco_ctx* ctx, const disco_c32* X, const disco_c32* z0, const disco_c32* z1, const float* mask, const int32_t* frames, int64_t R,
+                    int K, int M, int T, int F, int mic, int n_zsig, int skip, float* bank, int64_t N, int Tb, int64_t seg0, disco_stream s);
+
 /* MaxPool2d((1, 4)) of the CRNN's convolutional stack (dnn/models/crnn.py via nn_structures.py): floor-mode maximum over groups
  * of 4 along the last axis, plus the preceding convolution's per-channel bias (a constant commutes with the maximum; adding it here
  * spares a pass over the four times larger un-pooled map).  x [B][channels][rows_per_channel][row_len] seen as n_rows rows ->
