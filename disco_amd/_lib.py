@@ -35,6 +35,11 @@ class DiscoRefOutputs(C.Structure):
     _fields_ = [(nm, C.c_void_p) for nm in ('yf', 'sf', 'nf', 'z_y', 'z_s', 'z_n', 'zn', 'masks_z', 'mask_w')]
 
 
+class DiscoOnlineCompanion(C.Structure):
+    """struct disco_online_companion: one companion of disco_online_mwf_ref (X, Z or NULL, out)."""
+    _fields_ = [('X', C.c_void_p), ('Z', C.c_void_p), ('out', C.c_void_p)]
+
+
 MASK_FOR_Z = {'local': 0, None: 1, 'distant': 2, 'compressed': 3, 'use_oracle_refs': 4, 'use_oracle_zs': 5, 'previous': 6}
 
 # name -> (restype, argtypes); every symbol the header declares
@@ -137,6 +142,9 @@ PROTOTYPES = {
     'disco_selftest_staged_step2': (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     'disco_selftest_pending_matrices': (_int, [_vp, _vp, _vp, _vp]),
     'disco_tango_online': (_int, [_vp, _vp, _vp, _vp, _f, _int, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'disco_online_mwf_ref': (_int, [_vp, _vp, _vp, _vp, _int, _f, _f, _int, _f, _vp, _vp, C.POINTER(DiscoOnlineCompanion), _int, _vp]),
+    'disco_online_reference_workspace_bytes': (_sz, [_vp]),
+    'disco_tango_online_reference': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _int, _f, C.POINTER(DiscoRefOutputs), _vp, _vp, _sz, _vp]),
     'disco_online_state_bytes': (_sz, [_vp]),
     'disco_online_stream_workspace_bytes': (_sz, [_vp, _int]),
     'disco_tango_online_stream': (_int, [_vp, _vp, _int, _vp, _vp, _f, _int, _f, _i64, _int, _vp, _vp, _vp, _sz, _vp]),

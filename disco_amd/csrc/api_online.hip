@@ -1,29 +1,23 @@
 // libdisco_hip.so -- host side of the C ABI declared in include/disco_hip.h (gfx950 only): online / adaptive mode
-#include "host.h"
-#include "k_online.h"
+#include "online_host.h"
 
 using namespace disco;
 using namespace disco_host;
 
 // ---- online / adaptive mode ------------------------------------------------------------------------------
 
-// frames: the walk of this call (see OnlineArgs): T frames, planes of Tx (X, from frame tx0) / Tm (Z, mask, out) frames; state / init / phase:
-// the resumable recursion of the streaming form (NULL / 0 / 0: a whole clip from Rss = 0, Rnn = init_diag I)
-struct OnlineWalk {
-    int T, Tx, tx0, Tm;
-    c32* state;
-    int init, phase;
-};
-static int online_mwf_walk(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, const float* mask, int P, float lambda_cor, float mu,
-                           int update_every, float init_diag, disco_c32* out, disco_c32* w_last, const OnlineWalk& wk, disco_stream s) {
+namespace disco_host {
+int online_args(disco_ctx* ctx, const char* who, const disco_c32* X, const disco_c32* Z, const float* mask, int P, float lambda_cor, float mu,
+                int update_every, float init_diag, disco_c32* out, disco_c32* w_last, const OnlineWalk& wk, OnlineArgs* args) {
     const disco_cfg& c = ctx->cfg;
-    if (!X || !mask || !out) return fail(ctx, DISCO_E_ARG, "disco_online_mwf: null argument");
-    if (P != c.mics && P != c.mics + c.nodes - 1) return fail(ctx, DISCO_E_ARG, "disco_online_mwf: P must be mics or mics + nodes - 1");
-    if (P > c.mics && !Z) return fail(ctx, DISCO_E_ARG, "disco_online_mwf: P > mics needs the exchanged z");
+    auto refuse = [&](int code, const char* why) { return fail(ctx, code, (std::string(who) + why).c_str()); };
+    if (!X || !mask || !out) return refuse(DISCO_E_ARG, ": null argument");
+    if (P != c.mics && P != c.mics + c.nodes - 1) return refuse(DISCO_E_ARG, ": P must be mics or mics + nodes - 1");
+    if (P > c.mics && !Z) return refuse(DISCO_E_ARG, ": P > mics needs the exchanged z");
     if (!(lambda_cor >= 0.f && lambda_cor < 1.f) || update_every < 1 || !(init_diag > 0.f))
-        return fail(ctx, DISCO_E_ARG, "disco_online_mwf: need 0 <= lambda < 1, update_every >= 1, init_diag > 0");
-    if (P > 16) return fail(ctx, DISCO_E_UNSUPPORTED, "disco_online_mwf: P must be <= 16");
-    OnlineArgs a;
+        return refuse(DISCO_E_ARG, ": need 0 <= lambda < 1, update_every >= 1, init_diag > 0");
+    if (P > 16) return refuse(DISCO_E_UNSUPPORTED, ": P must be <= 16");
+    OnlineArgs& a = *args;
     a.X = (const c32*)X;
     a.Z = P > c.mics ? (const c32*)Z : nullptr;
     a.mask = mask;
@@ -48,6 +42,14 @@ static int online_mwf_walk(disco_ctx* ctx, const disco_c32* X, const disco_c32* 
     a.n_prob = (long long)c.rooms * ctx->Kl * ctx->F;
     a.zblk = ctx->zblk;
     a.R = c.rooms;
+    return 0;
+}
+}  // namespace disco_host
+
+static int online_mwf_walk(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, const float* mask, int P, float lambda_cor, float mu,
+                           int update_every, float init_diag, disco_c32* out, disco_c32* w_last, const OnlineWalk& wk, disco_stream s) {
+    OnlineArgs a;
+    if (int rc = online_args(ctx, "disco_online_mwf", X, Z, mask, P, lambda_cor, mu, update_every, init_diag, out, w_last, wk, &a)) return rc;
     hipStream_t st = (hipStream_t)s;
     // P <= 4, and 5 <= P <= 7 under option "solve_thread": one thread per (room, node, bin) (the float64 solve in the registers of one thread,
     // AGPRs as its second register file: k_solve_small.h)

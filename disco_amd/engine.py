@@ -229,6 +229,54 @@ class Engine:
                                               self.stream))
         return out, z, yf
 
+    def online_mwf_ref(self, X, mask, S, N=None, Z=None, Zs=None, Zn=None, lambda_cor=0.95, mu=None, update_every=1, init_diag=1e-3,
+                       want_w=False):
+        """online_mwf with companions (disco_online_mwf_ref): S [, N] laid out as X and Zs [, Zn] as Z ride through the same per-frame
+        filters as the mixture.  -> out, out_s[, out_n][, w_last]; out and w_last are those of online_mwf, bit for bit."""
+        P = self.M + (self.K - 1 if Z is not None else 0)
+        px, kx = self.to_device(X, np.complex64)
+        pz, kz = self.to_device(Z, np.complex64)
+        pm, km = self.to_device(mask, np.float32)
+        out = self.empty((self.R, self.Kl, self.T, self.F), np.complex64)
+        w = self.empty((self.R, self.Kl, self.F, P), np.complex64) if want_w else None
+        pairs = [(S, Zs)] + ([(N, Zn)] if N is not None else [])
+        comp = (L.DiscoOnlineCompanion * len(pairs))()
+        keep, outs = [], []
+        for i, (A, ZA) in enumerate(pairs):
+            pa, ka = self.to_device(A, np.complex64)
+            pza, kza = self.to_device(ZA, np.complex64)
+            o = self.empty((self.R, self.Kl, self.T, self.F), np.complex64)
+            comp[i].X, comp[i].Z, comp[i].out = pa, pza, o.ptr
+            keep += [ka, kza]
+            outs.append(o)
+        self._chk(self.lib.disco_online_mwf_ref(self.ctx, px, pz, pm, P, lambda_cor, self.cfg.mu if mu is None else mu, update_every,
+                                                init_diag, out.ptr, _ptr(w), comp, len(pairs), self.stream))
+        return (out, *outs, w) if want_w else (out, *outs)
+
+    def tango_online_reference(self, y, s, n, mask_z=None, mask_w=None, lambda_cor=0.95, update_every=1, init_diag=1e-3, want=None,
+                               signals=False):
+        """tango_reference's nine outputs in online mode, in ONE device-resident call (disco_tango_online_reference): y, s, n (R,K,M,L)
+        float32; mask_z / mask_w (R,K,T,F) float32 or None (oracle TF masks of the engine's mask type).  Returns {name: DevBuf (R,K,T,F)}
+        for the names in `want` (default: all nine); signals=True adds 'signals', a DevBuf (6,R,K,L): the inverse transforms of
+        yf, sf, nf, z_y, z_s, z_n -- what results_io.batch_results takes as sh_t, sf_t, nf_t, szh_t, szf_t, nzf_t.  signals may also be a
+        caller-owned device array of that shape (a torch tensor, which batch_results reads in place) to write them into."""
+        names = [nm for nm in ('z_y', 'z_s', 'z_n', 'zn', 'masks_z', 'yf', 'sf', 'nf', 'mask_w') if want is None or nm in want]
+        py, ky = self.to_device(y, np.float32)
+        ps, ks = self.to_device(s, np.float32)
+        pn, kn = self.to_device(n, np.float32)
+        pmz, kmz = self.to_device(mask_z, np.float32)
+        pmw, kmw = self._alias(mask_w, mask_z, (pmz, kmz), np.float32, none='null')         # None is the oracle mask, not mask_z
+        bufs = {nm: self.empty((self.R, self.K, self.T, self.F), np.float32 if nm.startswith('mask') else np.complex64) for nm in names}
+        outs = L.DiscoRefOutputs(**{nm: b.ptr for nm, b in bufs.items()})
+        want_sig = signals is not False and signals is not None
+        sig, psig, ksig = self._out(None if signals is True else signals, (6, self.R, self.K, self.Lsamp), np.float32, 'shape') if want_sig \
+            else (None, None, None)
+        self._chk(self.lib.disco_tango_online_reference(self.ctx, py, ps, pn, pmz, pmw, lambda_cor, update_every, init_diag, C.byref(outs),
+                                                        psig, None, 0, self.stream))
+        if want_sig:
+            bufs['signals'] = sig
+        return bufs
+
     def online_stream(self, lambda_cor=0.95, update_every=1, init_diag=1e-3):
         """A stream of the online two-step path (disco_tango_online_stream): `push(y_new, mask_z, mask_w=None, last=False)` consumes the
         next n_hops * hop samples of every channel, y_new (R, K, M, n_hops * hop), with the masks (R, K, n_new, F) of the frames it

@@ -262,6 +262,56 @@ def offline_tango(y, s, n, vads='irm1', mods=None, mask_for_z=MASK_Z, z_sigs='zs
     return tuple([np.ascontiguousarray(d[nm][0, k].T) for k in range(K)] for nm in names)
 
 
+def online_tango_batched(y, s, n, vads='irm1', masks=None, lambda_cor=0.95, update_every=1, init_diag=1e-3, n_fft=N_FFT,
+                         pad_mode='reflect', ref_mic=0, mu=1.0, signals=False):
+    """`offline_tango_batched` in the online / adaptive mode (mask_for_z='local', the only mode the recursion has): y, s, n (R, K, M, L)
+    float32 -> the same dict of nine arrays (R, K, T, F), the target and the noise image carried through the per-frame filters of the
+    mixture, in ONE library call (disco_tango_online_reference).  vads: a TF mask type, or a pair of them for the two steps;
+    masks=(mask_z, mask_w), arrays (R, K, T, F), override it -- this is how 'ivad' or a network's masks come in (mask_w None: mask_z).
+    signals=True adds 'signals' (6, R, K, L): the time signals of yf, sf, nf, z_y, z_s, z_n, a DevBuf where y, s, n were device
+    resident, else a NumPy array; signals=<a device array of that shape> (a torch tensor) has them written there and returned as given,
+    which is what results_io.batch_results reads in place.  Device-resident y, s, n are read in place."""
+    tf = lambda v: isinstance(v, str) and len(v) == 4 and v[:-1] in ('irm', 'ibm', 'iam') and v[3].isdigit()
+    pair = [vads, vads] if isinstance(vads, str) else list(vads)[:2]
+    if masks is None and not all(tf(v) for v in pair):
+        raise NotImplementedError(f'online_tango: vads={vads!r} is not a TF mask type ("irmX", "ibmX", "iamX"); '
+                                  "pass the masks of any other kind ('ivad', a network) as masks=(mask_z, mask_w)")
+    on_device = lambda a: hasattr(a, 'data_ptr') or hasattr(a, 'ptr')
+    dev_in = any(on_device(a) for a in (y, s, n))
+    y, s, n = (a if on_device(a) else np.ascontiguousarray(a, dtype=np.float32) for a in (y, s, n))
+    R, K, M, L = (int(v) for v in y.shape)
+    eng = get_engine(rooms=R, nodes=K, mics=M, length=L, n_fft=n_fft, mask=pair[0] if tf(pair[0]) else 'irm1', pad_mode=pad_mode,
+                     ref_mic=ref_mic, mu=mu, staged_step2=True)
+    if masks is not None:
+        mz, mw = (tuple(masks) + (None,))[:2]
+        mw = mz if mw is None else mw
+    else:
+        mz = mw = None                                                         # the library's own oracle masks
+        if pair[1] != pair[0]:                                                 # another TF type at step 2: prepared outside, as offline
+            if dev_in:
+                raise NotImplementedError('device-resident y, s, n need one TF mask type for both steps (or masks=)')
+            mz = eng.mask_oracle(np.ascontiguousarray(s[:, :, ref_mic].reshape(R * K, L)),
+                                 np.ascontiguousarray(n[:, :, ref_mic].reshape(R * K, L))).reshape(R, K, eng.T, eng.F)
+            mw = _time_mask(eng, pair[1], s[:, :, 0], n[:, :, 0], n_fft=n_fft, pad_mode=pad_mode)
+    d = eng.tango_online_reference(y, s, n, mask_z=mz, mask_w=mw, lambda_cor=lambda_cor, update_every=update_every, init_diag=init_diag,
+                                   signals=signals)
+    return {k: (v if k == 'signals' and (dev_in or on_device(signals)) else v.numpy()) for k, v in d.items()}
+
+
+def online_tango(y, s, n, vads='irm1', masks=None, lambda_cor=0.95, update_every=1, init_diag=1e-3):
+    """`offline_tango`'s call surface in the online / adaptive mode: (yf, sf, nf, z_y, z_s, z_n, zn, masks_z, mask_w), each a list over
+    nodes of (F, T) arrays.  masks=(mask_z, mask_w): per-node lists of (F, T) arrays or (K, F, T) arrays overriding `vads`."""
+    names = ['yf', 'sf', 'nf', 'z_y', 'z_s', 'z_n', 'zn', 'masks_z', 'mask_w']
+    yb, sb, nb = _as_batch(y), _as_batch(s), _as_batch(n)
+    if yb is None or sb is None or nb is None:
+        raise NotImplementedError('online_tango: nodes with different channel counts are not supported')
+    if masks is not None:                                                      # (F, T) per node -> the engine's (1, K, T, F)
+        masks = tuple(None if m is None else np.ascontiguousarray(np.stack([np.asarray(mk, np.float32).T for mk in m])[None]) for m in masks)
+    d = online_tango_batched(yb, sb, nb, vads=vads, masks=masks, lambda_cor=lambda_cor, update_every=update_every, init_diag=init_diag)
+    K = d['yf'].shape[1]
+    return tuple([np.ascontiguousarray(d[nm][0, k].T) for k in range(K)] for nm in names)
+
+
 def offline_tango_rooms(rooms, vads='irm1', mask_for_z=MASK_Z, n_fft=N_FFT, pad_mode='reflect', ref_mic=0, mu=1.0, mods=None, z_sigs='zs_hat'):
     """`offline_tango` for a list of rooms whose clips differ in length, in ONE batched call: `rooms` is a list of (y, s, n), each in
     the reference's [node][channel] -> time form, all with the same node and channel counts.  Returns a list with the reference's

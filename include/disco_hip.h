@@ -451,6 +451,43 @@ int disco_tango_online(disco_ctx* ctx, const float* y, const float* mask_z, cons
                        float* out, disco_c32* z_y, disco_c32* yf,
                        void* workspace, size_t workspace_bytes, disco_stream s);
 
+/* ---- scoring the online mode: companions through the per-frame filters ---------------------------------------------------------------
+ * Every score of the reference (tango.py:541-593) needs the target image and the noise image carried through the SAME filters as the
+ * mixture.  Online the filter changes at every update, and a filter history for a second pass would be P times the size of the output,
+ * so the companions ride through the walk itself: disco_online_mwf with one or two further inputs laid out as X / Z,
+ *     out^c_t = w_t^H v^c_t ,   v^c_t = [X^c_k(t,f,:) ; Z^c_j(t,f) j<k ; Z^c_j(t,f) j>k] ,
+ * w_t the filter in force at frame t.  Companions never enter Rss, Rnn or the solve: out and w_last are those of disco_online_mwf on
+ * the same inputs, route and options, bit for bit, and a non-finite companion value stays in its own output at its own frame.
+ * comp[i].X [R][Kl][T][F][M]; comp[i].Z [R][K][T][F] in the layout of Z (disco_set_z_blocks; needed iff P = M + K - 1);
+ * comp[i].out [R][Kl][T][F].  Node shards as for disco_online_mwf.  Argument rules of disco_online_mwf; in addition DISCO_E_ARG for
+ * n_comp other than 1 or 2, a companion without X or out, P > mics with a companion's Z missing.  A refusal writes nothing.
+ * Kernels: k_online_mwf_thread_ref<P, SQ32> and k_online_mwf_ref<P> (csrc/k_online.h), on the routes of disco_online_mwf. */
+typedef struct disco_online_companion {
+    const disco_c32* X;
+    const disco_c32* Z;
+    disco_c32* out;
+} disco_online_companion;
+int disco_online_mwf_ref(disco_ctx* ctx, const disco_c32* X, const disco_c32* Z, const float* mask, int P,
+                         float lambda_cor, float mu, int update_every, float init_diag,
+                         disco_c32* out, disco_c32* w_last, const disco_online_companion* comp, int n_comp, disco_stream s);
+
+/* disco_tango_reference's nine outputs in online mode (mask_for_z = 'local', the only mode the online recursion has): disco_stft of
+ * y, s, n; the masks (NULL: the oracle TF mask of cfg.mask_type from S, N, at cfg.ref_mic for step 1 and at channel 0 for step 2);
+ * online step 1 with companions -> z_y, z_s, z_n; zn = Y[ref] - z_y; online step 2 on [Y_k ; z_y,j] with companions [S_k ; z_s,j] and
+ * [N_k ; z_n,j] -> yf, sf, nf.  The exchanged rows are complex64.  A single node under one mask: step 2 repeats step 1 and is skipped.
+ *   out       device pointers, each [R][K][T][F]; any of them may be NULL (not wanted)
+ *   time_out  float [6][R][K][L] or NULL: the inverse transforms of yf, sf, nf, z_y, z_s, z_n in that order -- the six signals the
+ *             scores take
+ *   workspace at least disco_online_reference_workspace_bytes(ctx), or NULL for the context's own (disco_reserve(ctx, 2) covers it)
+ * With the workspace reserved the call allocates nothing and synchronises nothing: a fixed launch sequence that may be captured in a
+ * graph.  DISCO_E_UNSUPPORTED: per-room lengths set, a node shard active, mics + nodes - 1 > 16.
+ * Stage timers: stft, masks, online1_ref, online2_ref, istft. */
+size_t disco_online_reference_workspace_bytes(const disco_ctx* ctx);
+int disco_tango_online_reference(disco_ctx* ctx, const float* y, const float* s, const float* n, const float* mask_z_in,
+                                 const float* mask_w_in, float lambda_cor, int update_every, float init_diag,
+                                 const disco_ref_outputs* out, float* time_out,
+                                 void* workspace, size_t workspace_bytes, disco_stream st);
+
 /* The online two-step path as a STREAM -- state in, state out ("streaming latency instead of batch"; the reference's
  * primitive is a one-frame update, se_utils/internal_formulas.py:84-103).  One call consumes n_hops hops of NEW samples per channel and
  * emits every output sample that became final:
